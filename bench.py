@@ -6,7 +6,8 @@ region starts:
   (a) K1  greedy clustering at 0.8 identity of the non-redundant protein set  -> proteins/s  (M1)
   (b) K3  1000 pan/core rarefaction iterations on a 150,000 x 400 presence matrix -> iters/s (M2)
 
-  python bench.py [--gpus N --steps K --warmup W] [--workload cfg-3s|cfg-4|cfg-2s|small|tiny]
+  python bench.py [--gpus N --steps K --warmup W] [--workload cfg-3s|cfg-4|cfg-2s|small|tiny] [--full]
+                  [--dump-outputs DIR]
 
 N = 1: the 400-genome workload the metric is quoted on (BASELINE.json configs[2]; the Bacteroides
 files are not available offline, so the deterministic synthetic stand-in `cfg-3s` of SURVEY.md 8d:
@@ -22,10 +23,18 @@ torch.distributed.run --nproc-per-node N ... bench.py ...`, before this process 
 relays its JSON line and exit code); under a launcher (RANK / WORLD_SIZE in the environment) it is
 one of the ranks and WORLD_SIZE must equal --gpus.
 
-`value` is proteins/s of (a): sequences handed to the clustering call / its time. Beside the timed
-steps, rank 0 measures once each (reported, never part of `value`): the host-pointer entry point
-(H2D included), M2 through estimate_pan_core_size() (permutations, upload, DataFrame included), the
-end-to-end build_cds_pangenome() wall time, and the CPU oracle on a bounded sample.
+`value` is proteins/s of (a): sequences handed to the clustering call / its time. A plain run sets up,
+warms up, times the steps and prints the line. `--full` adds what rank 0 measures or checks once
+beside the timed steps (reported, never part of `value`): parity checks of the timed result against the
+oracle, one more step with events on every kernel (`kernels_ms_per_step`, `roofline`), the host-pointer
+entry point (H2D included), the call without work counters, M2 through estimate_pan_core_size()
+(permutations, upload, DataFrame included), the end-to-end build_cds_pangenome() wall time, the
+one-GPU point of the cfg-4 series, the unsharded run beside a sharded one (`one_gpu_ms`), and the CPU
+oracle on a bounded sample.
+
+`--dump-outputs DIR` writes, after the timed steps, what the last timed step returned as DIR/<name>.npy
+(float64; identities float32): the clustering's cluster / member / identity / strand arrays,
+n_clusters and its work counters (STAT_FIELDS without `sweeps`), and the pan / core tables.
 """
 import argparse
 import json
@@ -43,6 +52,7 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0   # gfx950 spec, /opt/skills/guides/MI355X_MICROARCH.md
 L2_PEAK_GBS = 34500.0   # aggregate L2, same guide
 PMC_SUMMARY = os.path.join('profiles', 'r03_pmc_summary_cfg3s.json')
+DUMP_BYTES = 64 << 20   # --dump-outputs: at most this much in all
 
 
 def log(*a):
@@ -110,6 +120,38 @@ def cdhit_reference(sres, soff, got_cluster, got_member, workdir):
     return out
 
 
+def dump_outputs(out_dir, clustered, pan, core, limit=DUMP_BYTES):
+    """--dump-outputs: the clustering result of the last timed step (None under --only pancore) and its pan / core
+    tables (None under --only cluster) as <out_dir>/<name>.npy. Integers are written as float64 (exact), identities
+    as float32. Over `limit` bytes in all, the same seeded share of rows is kept of every per-sequence and every
+    per-iteration array, and the rows kept are written beside them (sequence_index.npy / iteration_index.npy)."""
+    from pangenomix_amd._native import STAT_FIELDS
+    os.makedirs(out_dir, exist_ok=True)
+    whole, groups = {}, []
+    if clustered is not None:
+        cl, mem, iden, strand, n_clusters, st = clustered
+        groups.append(('sequence_index', {'cluster': np.asarray(cl, np.float64), 'member': np.asarray(mem, np.float64),
+                                          'identity': np.asarray(iden, np.float32),
+                                          'strand': np.asarray(strand, np.float64)}))
+        # the counters of the sequential rule; `sweeps` (windows) is the implementation's own choice
+        whole.update(n_clusters=np.array([n_clusters], np.float64),
+                     stats=np.array([st[k] for k in STAT_FIELDS if k != 'sweeps'], np.float64))
+    if pan is not None:
+        groups.append(('iteration_index', {'pan': np.asarray(pan, np.float64), 'core': np.asarray(core, np.float64)}))
+    room = limit - 4096 * (len(whole) + 6) - sum(a.nbytes for a in whole.values())   # (npy headers)
+    need = sum(len(next(iter(g.values()))) * (8 + sum(a.itemsize * a[:1].size for a in g.values())) for _, g in groups)
+    for index_name, g in groups:
+        rows = len(next(iter(g.values())))
+        if need > room:
+            keep = np.sort(np.random.default_rng(0).choice(rows, rows * room // need, replace=False))
+            g = {k: a[keep] for k, a in g.items()}
+            whole[index_name] = keep.astype(np.float64)
+        whole.update(g)
+    for name, a in whole.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    return sorted(whole)
+
+
 def launch_ranks(n):
     """`python bench.py --gpus N` without a launcher: start the N ranks as a CHILD process (never exec: this
     process must not have touched a GPU, and it has not) and relay its output and exit code."""
@@ -149,9 +191,16 @@ def main():
                          'callback, or the library\'s own ncclAllGather (pgx_rccl_*); RCCL over xGMI either way')
     ap.add_argument('--only', choices=['all', 'cluster', 'pancore'], default='all',
                     help='restrict the step (used for rocprofv3 counter passes); the JSON line needs all')
+    ap.add_argument('--full', action='store_true',
+                    help='also the once-only measurements and checks beside the timed steps (parity, per-kernel table, '
+                         'roofline, entry points, end to end, cfg-4, CPU baseline); a plain run times the steps only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed as DIR/<name>.npy')
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit('--gpus must be at least 1')
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit('--steps must be at least 1 and --warmup at least 0')
     if 'WORLD_SIZE' not in os.environ and 'RANK' not in os.environ:
         if args.gpus > 1:
             raise SystemExit(launch_ranks(args.gpus))
@@ -275,11 +324,6 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     prof = ctx.profile_read()
-    # one more, untimed, step with events on every clustering kernel: the per-kernel table
-    ctx.profile_reset()
-    step(profile_cluster=True)
-    prof_all = ctx.profile_read()
-    ctx.profile(False)
     if use_dist:
         t = torch.tensor([dt, t_cluster, t_pancore], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -294,24 +338,44 @@ def main():
             return f
         last['cluster'] = cluster.merge_shard_results(last['cluster'], host_reduce(dist.ReduceOp.SUM),
                                                       host_reduce(dist.ReduceOp.MAX))
+    if args.dump_outputs:   # d_pan / d_core still hold the last timed step
+        pan_last = core_last = None
+        if args.only != 'cluster':
+            pan_last, core_last = d_pan[:my_iter], d_core[:my_iter]
+            if sharded:   # each rank holds its own iterations: assemble all of them
+                pan_last, core_last = (torch.zeros((n_iter, S), dtype=torch.int32, device=dev) for _ in range(2))
+                pan_last[it_lo:it_hi], core_last[it_lo:it_hi] = d_pan[:my_iter], d_core[:my_iter]
+                dist.all_reduce(pan_last)
+                dist.all_reduce(core_last)
+            pan_last, core_last = pan_last.cpu().numpy(), core_last.cpu().numpy()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, last.get('cluster'), pan_last, core_last)
+    prof_all = None
+    if args.full:   # one more, untimed, step with events on every clustering kernel: the per-kernel table
+        timed = dict(last)
+        ctx.profile_reset()
+        step(profile_cluster=True)
+        prof_all = ctx.profile_read()
+        ctx.profile(False)
+        last.update(timed)   # (what follows reports and checks the timed step's result)
 
     if args.only != 'all':
         if rank == 0:
             log('--only %s: %d step(s) done in %.3f s (no JSON line)' % (args.only, args.steps, dt))
-            for k_, v in sorted(prof_all.items(), key=lambda kv: -kv[1][0]):
+            for k_, v in sorted((prof_all or {}).items(), key=lambda kv: -kv[1][0]):
                 log('  %-24s %9.3f ms %6d launches' % (k_, v[0], v[1]))
         if use_dist:
             dist.destroy_process_group()
         ctx.close()
         return
 
-    # ---- once-only measurements beside the timed steps (rank 0; the other ranks wait at the barrier) ------
+    # ---- --full: once-only measurements beside the timed steps (rank 0; the other ranks wait at the barrier) ------
+    terms = cluster_terms(last['cluster'][5])
     extra = {}
-    if rank == 0:
+    if rank == 0 and args.full:
         import oracle
         import scipy.sparse
         from pangenomix_amd import pangenome, sparse_utils
-        steps = args.steps
         cl, mem, iden, _, n_clusters, st = last['cluster']
         # parity spot checks of what was just timed (the oracle is the checker only)
         if my_iter:
@@ -459,9 +523,6 @@ def main():
         pc_bytes = my_iter * (S * words * 8 + 2 * S * 4) + my_iter * S * 4
         sweep_ms = prof['pan_core_sweep_kernel'][0] / prof['pan_core_sweep_kernel'][1] if my_iter else float('nan')
         pc_gbs = pc_bytes / (sweep_ms * 1e-3) / 1e9
-        terms = cluster_terms(st)
-        cl_bytes = sum(terms.values())
-        cl_gbs = cl_bytes / (t_cluster / steps) / 1e9
         pmc, pmc_src = {}, None
         if os.path.exists(os.path.join(ROOT, PMC_SUMMARY)):
             pmc = json.load(open(os.path.join(ROOT, PMC_SUMMARY))).get('kernels', {})
@@ -504,7 +565,7 @@ def main():
                        'avg_kernel_ms': sweep_ms, 'algorithmic_bytes_per_launch': pc_bytes,
                        'note': 'the 7.5 MB matrix is L2-resident by design (XCD striping), so the roof is the aggregate L2 '
                                '(34.5 TB/s); the same bytes against the 8 TB/s HBM peak are given beside it'}
-        extra.update(kern=kern, terms=terms, cl_bytes=cl_bytes, cl_gbs=cl_gbs, roofline=roofline, roofline_pc=roofline_pc)
+        extra.update(kern=kern, roofline=roofline, roofline_pc=roofline_pc)
 
         cpu = None
         if not args.skip_cpu and world == 1:   # (the CPU baseline is taken at N = 1 only)
@@ -545,6 +606,8 @@ def main():
     if rank == 0:
         steps = args.steps
         cl, mem, iden, _, n_clusters, st = last['cluster']
+        cl_bytes = sum(terms.values())
+        cl_gbs = cl_bytes / (t_cluster / steps) / 1e9
         jobs = 1 if (sharded or world == 1) else world   # independent jobs running side by side
         line = {
             'metric': 'proteins/sec clustered at 0.8 identity + pan/core iters/sec, 400-genome set',
@@ -562,21 +625,22 @@ def main():
                                           else 'torch.distributed, nccl backend')) if sharded
                        else ('replicas x%d' % world if world > 1 else 'one GPU')},
             'pan_core': {'value': jobs * n_iter * steps / t_pancore, 'unit': 'iters/s',
-                         'ms': t_pancore / steps * 1e3, 'roofline': extra['roofline_pc'],
+                         'ms': t_pancore / steps * 1e3, 'roofline': extra.get('roofline_pc'),
                          'entry_point': extra.get('pan_core_entry_point')},
             'cluster': {'ms': t_cluster / steps * 1e3, 'raw_records_per_s': jobs * n_raw * steps / t_cluster,
                         'host_pointer_ms': extra.get('host_pointer_ms'),
                         'without_counters_ms': extra.get('without_counters_ms'),
-                        'algorithmic_bytes': extra['cl_bytes'], 'algorithmic_terms': extra['terms'],
-                        'achieved_GBs': extra['cl_gbs'], 'frac_hbm': extra['cl_gbs'] / HBM_PEAK_GBS,
+                        'algorithmic_bytes': cl_bytes, 'algorithmic_terms': terms,
+                        'achieved_GBs': cl_gbs, 'frac_hbm': cl_gbs / HBM_PEAK_GBS,
                         'dp_cells_per_s': st['dp_cells'] / (t_cluster / steps), 'stats': st},
             'one_gpu_ms': extra.get('one_gpu_ms'),
             'speedup_vs_one_gpu': (extra['one_gpu_ms'] / (t_cluster / steps * 1e3)) if extra.get('one_gpu_ms') else None,
             'end_to_end': extra.get('end_to_end'),
             'cfg4_one_gpu': extra.get('cfg4_one_gpu'),
-            'roofline': extra['roofline'],
-            'cpu_baseline': extra['cpu'],
-            'kernels_ms_per_step': {k_: {'ms': round(v[0], 4), 'launches': v[1]} for k_, v in sorted(extra['kern'].items())},
+            'roofline': extra.get('roofline'),
+            'cpu_baseline': extra.get('cpu'),
+            'kernels_ms_per_step': {k_: {'ms': round(v[0], 4), 'launches': v[1]} for k_, v in sorted(extra['kern'].items())}
+                                   if 'kern' in extra else None,
         }
         print(json.dumps(line), flush=True)
     if use_dist:
