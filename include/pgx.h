@@ -11,6 +11,8 @@
  *   pangenome_analysis.py:72-98         estimate_pan_core_size(): the Python double loop
  *                                       over scipy CSR rows -> pgx_presence_bitmap* +
  *                                       pgx_pan_core*
+ *   pangenome_analysis.py:101-166       compute_bernoulli_grid_core_genome(): the dense
+ *                                       numpy likelihood and gradient -> pgx_bernoulli_*
  *
  * The reference-side binding is a ctypes stub. Conventions:
  *   - every function returns 0 on success and a negative pgx_status on error;
@@ -360,6 +362,39 @@ int pgx_bitmap_from_clusters(pgx_ctx *ctx, const int32_t *cluster_of_group, uint
 int pgx_bitmap_resident_read(pgx_ctx *ctx, uint64_t token, uint64_t *out_bits);
 int pgx_pan_core_table_resident(pgx_ctx *ctx, uint64_t token, uint32_t n_genes, uint32_t n_genomes, uint32_t *mt_key,
                                 int32_t *mt_pos, uint32_t n_iter, int32_t *out_perms, double *out_table);
+
+/* Bernoulli grid likelihood (compute_bernoulli_grid_core_genome, reference pangenome_analysis.py:101-166): gene i occurs in
+ * genome j with probability p_i q_j. One evaluation at (P, Q) gives, for the binary table X,
+ *   LL      = sum_ij X_ij log(p_i q_j) + (1 - X_ij) log(1 - p_i q_j)
+ *   dL/dp_i = rowsum_i / p_i - sum_j (1 - X_ij) q_j / (1 - p_i q_j)
+ *   dL/dq_j = colsum_j / q_j - sum_i (1 - X_ij) p_i / (1 - p_i q_j)
+ * in fp64, with every cell's terms as these per-cell expressions give them (so nan / inf appear where they put them:
+ * p_i q_j = 1 on a present cell gives nan in LL and in that row's and column's gradient). Deterministic: the same
+ * inputs give the same bits on every call (no atomics; partials summed in an order fixed by the table's shape).
+ * When every fl(p_i q_j) lies strictly inside (0, 1) the present cells' log terms are summed as
+ * rowsum_i log p_i + colsum_j log q_j; flags = PGX_BERNOULLI_EXACT evaluates every cell's own log instead.
+ * pq = [P (n_genes); Q (n_genomes)], out = [LL; dL/dp (n_genes); dL/dq (n_genomes)].
+ *   pgx_bernoulli_eval_dev      d_bits: the table in the bitmap layout above (pad bits zero; they are not cells);
+ *                               DEVICE pointers and a caller workspace of pgx_bernoulli_workspace_bytes(); enqueues
+ *                               on `stream` only (no allocation, no sync)
+ *   pgx_bernoulli_load          uploads the table's COO coordinates once and keeps its bitmap in the context for the
+ *                               evaluations that follow; out_duplicates as pgx_presence_bitmap (may be NULL); a record
+ *                               out of range fails with PGX_ERR_INVALID
+ *   pgx_bernoulli_load_resident the same from the bitmap a pipeline left resident (pgx_bitmap_from_clusters), whose rows
+ *                               are cluster numbers: row i of the table is row row_map[i] of the resident bitmap
+ *                               (0 <= row_map[i] < its n_genes; n_genomes must equal its n_genomes). No upload of the
+ *                               table. A stale token fails with PGX_ERR_INVALID and leaves no table loaded.
+ *   pgx_bernoulli_eval          one evaluation of the loaded table from HOST pq into HOST out (n_genes + n_genomes
+ *                               and 1 + n_genes + n_genomes doubles) */
+#define PGX_BERNOULLI_EXACT 1u
+size_t pgx_bernoulli_workspace_bytes(uint32_t n_genes, uint32_t n_genomes);
+int pgx_bernoulli_eval_dev(pgx_ctx *ctx, const uint64_t *d_bits, uint32_t n_genes, uint32_t n_genomes, const double *d_pq,
+                           uint32_t flags, double *d_out, void *d_workspace, size_t workspace_bytes, void *stream);
+int pgx_bernoulli_load(pgx_ctx *ctx, const int32_t *rows, const int32_t *genomes, uint64_t n_records, uint32_t n_genes,
+                       uint32_t n_genomes, uint64_t *out_duplicates);
+int pgx_bernoulli_load_resident(pgx_ctx *ctx, uint64_t token, const int32_t *row_map, uint32_t n_genes,
+                                uint32_t n_genomes);
+int pgx_bernoulli_eval(pgx_ctx *ctx, const double *pq, uint32_t flags, double *out);
 
 /* feature names (pangenome.py:1944-1969) as fixed-width zero-padded ASCII records (numpy 'S<width>'):
  * <prefix><cluster>[<variant><member>]; variant NULL = gene names */

@@ -119,6 +119,11 @@ SIGNATURES = {
     'pgx_pan_core_workspace_bytes': (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_uint32]),
     'pgx_pan_core_dev': (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, _P, _P,
                                    C.c_size_t, _P]),
+    'pgx_bernoulli_workspace_bytes': (C.c_size_t, [C.c_uint32, C.c_uint32]),
+    'pgx_bernoulli_eval_dev': (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, _P, C.c_size_t, _P]),
+    'pgx_bernoulli_load': (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
+    'pgx_bernoulli_load_resident': (C.c_int, [_P, C.c_uint64, _P, C.c_uint32, C.c_uint32]),
+    'pgx_bernoulli_eval': (C.c_int, [_P, _P, C.c_uint32, _P]),
     'pgx_cluster_greedy': (C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(ClusterParams), _P, _P, _P, _P,
                                      C.POINTER(C.c_uint32), C.POINTER(ClusterStats)]),
     'pgx_cluster_window_cap': (C.c_uint32, [C.POINTER(ClusterParams)]),
@@ -412,6 +417,41 @@ class Context(object):
         check(lib().pgx_pan_core_table_resident(self._h, int(token), int(n_genes), int(n_genomes), _ptr(mt_key), C.byref(pos),
                                                 int(n_iter), _ptr(perms), _ptr(table)))
         return table, perms, int(pos.value)
+
+    # -- Bernoulli grid likelihood (compute_bernoulli_grid_core_genome) --------------------------------------------
+    def bernoulli_load(self, rows, genomes, n_genes, n_genomes):
+        """Upload the binary table's coordinates once; its bitmap stays in the context for bernoulli_eval().
+        Returns the number of duplicate coordinates."""
+        rows = np.ascontiguousarray(rows, dtype=np.int32)
+        genomes = np.ascontiguousarray(genomes, dtype=np.int32)
+        if rows.shape != genomes.shape or rows.ndim != 1:
+            raise ValueError('rows and genomes must be 1-D arrays of equal length')
+        dup = C.c_uint64(0)
+        check(lib().pgx_bernoulli_load(self._h, _ptr(rows), _ptr(genomes), rows.size, int(n_genes), int(n_genomes),
+                                       C.byref(dup)))
+        self._bern_shape = (int(n_genes), int(n_genomes))
+        return int(dup.value)
+
+    def bernoulli_load_resident(self, token, row_map, n_genomes):
+        """Load the table from the bitmap a pipeline left resident under `token`: row i of the table is row
+        row_map[i] (its cluster number) of that bitmap. Raises PgxError when the token is stale."""
+        row_map = np.ascontiguousarray(row_map, dtype=np.int32)
+        self._bern_shape = None
+        check(lib().pgx_bernoulli_load_resident(self._h, int(token), _ptr(row_map), row_map.size, int(n_genomes)))
+        self._bern_shape = (row_map.size, int(n_genomes))
+
+    def bernoulli_eval(self, pq, exact=False):
+        """[LL, dL/dp..., dL/dq...] (float64) of the loaded table at pq = [P; Q]. exact=True: every present cell's
+        own log (pgx.h: PGX_BERNOULLI_EXACT)."""
+        shape = getattr(self, '_bern_shape', None)
+        if shape is None:
+            raise PgxError('no table loaded (bernoulli_load / bernoulli_load_resident)')
+        pq = np.ascontiguousarray(pq, dtype=np.float64)
+        if pq.shape != (shape[0] + shape[1],):
+            raise ValueError('pq must hold n_genes + n_genomes values')
+        out = np.empty(pq.size + 1, dtype=np.float64)
+        check(lib().pgx_bernoulli_eval(self._h, _ptr(pq), 1 if exact else 0, _ptr(out)))
+        return out
 
     def pan_core(self, bits, n_genes, perms):
         perms = np.ascontiguousarray(perms, dtype=np.int32)

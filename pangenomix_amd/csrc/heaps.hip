@@ -66,7 +66,7 @@ __global__ __launch_bounds__(256) void heaps_fit_kernel(const T *__restrict__ pa
     if (lane == 0) { alpha[it] = a; kappa[it] = k; if (steps) steps[it] = n; }
 }
 
-enum { HP_SLOT_TAB = 90, HP_SLOT_A, HP_SLOT_K };
+enum { HP_SLOT_TAB = 96, HP_SLOT_A, HP_SLOT_K };   // (after pancore's 80-94: 90 is the resident bitmap)
 
 }  // namespace
 

@@ -293,6 +293,8 @@ __global__ __launch_bounds__(256) void row_counts_kernel(const unsigned long lon
 // K3 device buffers of the host-pointer entry points live in the context's grow-only workspace
 // (slots after the clustering's), so repeated calls neither allocate nor free.
 enum { PC_SLOT_ROWS = 80, PC_SLOT_GENOMES, PC_SLOT_BITS, PC_SLOT_PERMS, PC_SLOT_PAN, PC_SLOT_CORE, PC_SLOT_WS, PC_SLOT_CNT, PC_SLOT_COUNTS, PC_SLOT_TABLE, PC_SLOT_RESIDENT, PC_SLOT_RES_A, PC_SLOT_RES_B, PC_SLOT_RES_C, PC_SLOT_RES_D };
+static_assert(PC_SLOT_RESIDENT == PGX_SLOT_RESIDENT, "pgx_internal.h names the resident slot");
+static_assert(PC_SLOT_RES_D < 96, "pancore's slots end before the Heaps fit's");
 struct PcBuf : DevBuf {
     PcBuf(pgx_ctx *c, int s) { ctx = c; slot = s; }
 };

@@ -43,6 +43,9 @@ struct pgx_ctx {
     // the gene x genome bitmap a pipeline left on the device (pgx_bitmap_from_clusters): its token, shape, buffer
     uint64_t resident_token = 0, resident_next = 1;
     uint32_t resident_genes = 0, resident_genomes = 0;
+    // the table loaded for Bernoulli likelihood evaluations (pgx_bernoulli_load*): its shape; the bitmap is a workspace slot
+    uint32_t bern_genes = 0, bern_genomes = 0;
+    bool bern_loaded = false;
     // the library's own RCCL communicator (pgx_rccl_comm_create): the record-sharded exchange without a callback
     void *comm = nullptr;
     int comm_rank = 0, comm_world = 0;
@@ -148,6 +151,10 @@ struct DevBuf {
         return static_cast<T *>(p);
     }
 };
+
+// Workspace slot of the pipeline's resident bitmap (pancore.hip), read in place by bernoulli.hip. Slots in use:
+// pancore 80-94, heaps 96-98, bernoulli 100-107.
+constexpr int PGX_SLOT_RESIDENT = 90;
 
 static inline uint32_t ceil_div_u32(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
 

@@ -547,8 +547,9 @@ def _native_pipeline(genome_paths, nr_fasta, shared, missing, names_tsv, name, c
                 ctx = _native.default_context()
                 token = ctx.bitmap_from_clusters(cl, fs.group_of_record, fs.file_of_record, genome_of_file,
                                                  len(gene_order), len(genome_order))
+                # row_cluster: the bitmap row (cluster number) of each table row -- the names sort as strings
                 out[1]._pgx_resident = {'ctx': ctx, 'token': token, 'shape': out[1].shape, 'data': out[1].data,
-                                        'nnz': int(out[1].data.nnz)}
+                                        'nnz': int(out[1].data.nnz), 'row_cluster': c_sorted[new_gene].astype(np.int32)}
             except _native.PgxError as exc:       # (the tables are complete without it)
                 print('Note: no device-resident bitmap (%s)' % exc)
             lap('device-resident bitmap')

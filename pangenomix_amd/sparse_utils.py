@@ -214,3 +214,22 @@ class LightSparseDataFrame(object):
     @property
     def values(self):
         return self.data.toarray()
+
+    def to_sparse_arrays(self):
+        """pd.DataFrame with one pandas SparseArray column per genome (the older table format; reference :317-328):
+        each column stores the nonzero entries of its genome (dtype of .data) and has fill value NaN, as the
+        reference's frame has. Note: its .values are then not the table (absent cells read as NaN, or as the
+        smallest int64 once numpy casts them); compute_bernoulli_grid_core_genome reads such a frame by its stored
+        entries instead."""
+        import pandas as pd
+        csc = self.data.tocsc()                      # (duplicates summed, as a dense column would hold them)
+        n = self.shape[0]
+        columns = {}
+        for c, name in enumerate(self.columns):
+            lo, hi = csc.indptr[c], csc.indptr[c + 1]
+            col = np.zeros(n, dtype=csc.dtype)
+            col[csc.indices[lo:hi]] = csc.data[lo:hi]
+            arr = pd.arrays.SparseArray(col)         # stores the entries that differ from 0
+            arr.fill_value = np.nan
+            columns[name] = arr
+        return pd.DataFrame(data=columns, index=self.index)
