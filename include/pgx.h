@@ -13,6 +13,8 @@
  *                                       pgx_pan_core*
  *   pangenome_analysis.py:101-166       compute_bernoulli_grid_core_genome(): the dense
  *                                       numpy likelihood and gradient -> pgx_bernoulli_*
+ *   pangenome_analysis.py:457-492       ks_montecarlo_bbn() / draw_bbn(): np.random.choice
+ *                                       and the per-iteration eCDF loop -> pgx_bbn_*
  *
  * The reference-side binding is a ctypes stub. Conventions:
  *   - every function returns 0 on success and a negative pgx_status on error;
@@ -330,6 +332,10 @@ int pgx_fasta_write_clustered(const pgx_fasta_set *fs, const int32_t *cluster, c
  * numpy's legacy global generator (pangenome_analysis.py:84-85): MT19937 state key[624] / pos in, advanced
  * state out (np.random.get_state() / set_state()). out_perms: [n_iter][n] int32. */
 int pgx_legacy_shuffles(uint32_t *key, int32_t *pos, uint32_t n, uint32_t n_iter, int32_t *out_perms);
+/* the next n_words raw 32-bit outputs of numpy's legacy generator (MT19937 tempered words, in stream order; one
+ * random_sample() double is ((w0 >> 5) * 2^26 + (w1 >> 6)) / 2^53 of two of them), advancing key / pos as numpy does:
+ * a stream that ends on a block boundary leaves pos = 624 and the key un-twisted. Host only. */
+int pgx_legacy_uniform_words(uint32_t *key, int32_t *pos, uint64_t n_words, uint32_t *out);
 
 /* pgx_legacy_shuffles + pgx_pan_core_coo in one call (pangenome_analysis.py:51-98 from the binary table's
  * coordinates and the generator state): the draws are made on a host thread while the coordinates are uploaded and
@@ -395,6 +401,30 @@ int pgx_bernoulli_load(pgx_ctx *ctx, const int32_t *rows, const int32_t *genomes
 int pgx_bernoulli_load_resident(pgx_ctx *ctx, uint64_t token, const int32_t *row_map, uint32_t n_genes,
                                 uint32_t n_genomes);
 int pgx_bernoulli_eval(pgx_ctx *ctx, const double *pq, uint32_t flags, double *out);
+
+/* Monte-Carlo Kolmogorov-Smirnov test of a beta-binomial fit (ks_montecarlo_bbn / draw_bbn, reference
+ * pangenome_analysis.py:457-492). A draw is np.random.choice(arange(L), p=probs) of the legacy generator:
+ * u = random_sample() from two words (pgx_legacy_uniform_words), value = searchsorted(draw_cdf, u, side='right'), where
+ * draw_cdf = probs.cumsum() / its last element (L = sim_limit values, non-decreasing, last = 1). Iteration i takes draws
+ * [i n_samples, (i + 1) n_samples) of the stream; its statistic is
+ *   ks_sim[i] = max_j | cumsum(hist_i)[j] / n_samples - model_cdf[j] |      (j < L; fp64; nan propagates)
+ * with hist_i the histogram of its draws: every step exact or rounded once, so the result is the reference's bits.
+ *   pgx_bbn_ks_sim      HOST arrays; the words are generated on the host from key / pos (advanced as numpy would,
+ *                       2 n_samples iterations words) and streamed to the device in chunks of about chunk_draws draws
+ *                       (whole iterations, at least one; 0 = the library's default; results do not depend on it)
+ *   pgx_bbn_ks_sim_dev  d_words: the iterations' 2 n_samples words each, DEVICE pointers, a caller workspace of
+ *                       pgx_bbn_workspace_bytes() (zero bytes up to PGX_BBN_LDS_LIMIT values); enqueues on `stream` only
+ *   pgx_bbn_draws       the `size` values themselves (int64, as choice returns them), in chunks as above
+ * n_samples >= 1 and sim_limit >= 1. */
+#define PGX_BBN_LDS_LIMIT 4096u
+size_t pgx_bbn_workspace_bytes(uint32_t sim_limit, uint32_t iterations);
+int pgx_bbn_ks_sim_dev(pgx_ctx *ctx, const uint32_t *d_words, const double *d_draw_cdf, const double *d_model_cdf,
+                       uint32_t sim_limit, uint32_t n_samples, uint32_t iterations, double *d_ks_sim, void *d_workspace,
+                       size_t workspace_bytes, void *stream);
+int pgx_bbn_ks_sim(pgx_ctx *ctx, const double *draw_cdf, const double *model_cdf, uint32_t sim_limit, uint32_t n_samples,
+                   uint32_t iterations, uint32_t *mt_key, int32_t *mt_pos, uint64_t chunk_draws, double *out_ks_sim);
+int pgx_bbn_draws(pgx_ctx *ctx, const double *draw_cdf, uint32_t sim_limit, uint64_t size, uint32_t *mt_key,
+                  int32_t *mt_pos, uint64_t chunk_draws, int64_t *out_idx);
 
 /* feature names (pangenome.py:1944-1969) as fixed-width zero-padded ASCII records (numpy 'S<width>'):
  * <prefix><cluster>[<variant><member>]; variant NULL = gene names */

@@ -80,6 +80,7 @@ SIGNATURES = {
     'pgx_fasta_header_offsets': (_P, [_P]),
     'pgx_fasta_write_consolidated': (C.c_int, [_P, _S, _S, _S]),
     'pgx_legacy_shuffles': (C.c_int, [_P, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, _P]),
+    'pgx_legacy_uniform_words': (C.c_int, [_P, C.POINTER(C.c_int32), C.c_uint64, _P]),
     'pgx_pan_core_coo_rng': (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint32, C.c_uint32, _P, C.POINTER(C.c_int32), C.c_uint32,
                                       _P, _P, _P, C.POINTER(C.c_uint64)]),
     'pgx_pan_core_table': (C.c_int, [_P, _P, _P, _P, C.c_uint64, C.c_uint32, C.c_uint32, _P, C.POINTER(C.c_int32), C.c_uint32,
@@ -124,6 +125,11 @@ SIGNATURES = {
     'pgx_bernoulli_load': (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
     'pgx_bernoulli_load_resident': (C.c_int, [_P, C.c_uint64, _P, C.c_uint32, C.c_uint32]),
     'pgx_bernoulli_eval': (C.c_int, [_P, _P, C.c_uint32, _P]),
+    'pgx_bbn_workspace_bytes': (C.c_size_t, [C.c_uint32, C.c_uint32]),
+    'pgx_bbn_ks_sim_dev': (C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, C.c_size_t, _P]),
+    'pgx_bbn_ks_sim': (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, C.POINTER(C.c_int32),
+                                 C.c_uint64, _P]),
+    'pgx_bbn_draws': (C.c_int, [_P, _P, C.c_uint32, C.c_uint64, _P, C.POINTER(C.c_int32), C.c_uint64, _P]),
     'pgx_cluster_greedy': (C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(ClusterParams), _P, _P, _P, _P,
                                      C.POINTER(C.c_uint32), C.POINTER(ClusterStats)]),
     'pgx_cluster_window_cap': (C.c_uint32, [C.POINTER(ClusterParams)]),
@@ -221,6 +227,29 @@ def rccl_unique_id():
     buf = (C.c_uint8 * 128)()
     check(lib().pgx_rccl_unique_id(C.cast(buf, _P)))
     return bytes(buf)
+
+
+def _legacy_key(key):
+    if not (isinstance(key, np.ndarray) and key.dtype == np.uint32 and key.shape == (624,) and key.flags.c_contiguous):
+        raise ValueError('key must be a C-contiguous uint32[624] array')
+    return key
+
+
+def legacy_uniform_words(key, pos, n_words):
+    """(words uint32[n_words], pos): the next raw outputs of numpy's legacy generator from state (key, pos); key
+    (uint32[624], C-contiguous) is advanced IN PLACE. Host only: needs the library, not a device."""
+    _legacy_key(key)
+    out = np.empty(int(n_words), dtype=np.uint32)
+    p = C.c_int32(int(pos))
+    check(lib().pgx_legacy_uniform_words(_ptr(key), C.byref(p), int(n_words), _ptr(out)))
+    return out, int(p.value)
+
+
+def _bbn_args(draw_cdf, key, pos):
+    draw_cdf = np.ascontiguousarray(draw_cdf, dtype=np.float64)
+    if draw_cdf.ndim != 1 or draw_cdf.size == 0:
+        raise ValueError('draw_cdf must be a non-empty 1-D array')
+    return draw_cdf, _legacy_key(key), C.c_int32(int(pos))
 
 
 class Context(object):
@@ -452,6 +481,33 @@ class Context(object):
         out = np.empty(pq.size + 1, dtype=np.float64)
         check(lib().pgx_bernoulli_eval(self._h, _ptr(pq), 1 if exact else 0, _ptr(out)))
         return out
+
+    # -- Monte-Carlo KS test of a beta-binomial fit (ks_montecarlo_bbn / draw_bbn) -------------------------------------
+    def bbn_ks_sim(self, draw_cdf, model_cdf, n_samples, iterations, key, pos, chunk_draws=0):
+        """(ks_sim float64[iterations], pos): the KS statistic of every iteration's n_samples draws from the legacy
+        generator state (key uint32[624], advanced IN PLACE; pos), as pgx.h's pgx_bbn_ks_sim states it."""
+        draw_cdf, key, p = _bbn_args(draw_cdf, key, pos)
+        model_cdf = np.ascontiguousarray(model_cdf, dtype=np.float64)
+        if model_cdf.shape != draw_cdf.shape:
+            raise ValueError('draw_cdf and model_cdf must have the same length')
+        out = np.empty(int(iterations), dtype=np.float64)
+        check(lib().pgx_bbn_ks_sim(self._h, _ptr(draw_cdf), _ptr(model_cdf), draw_cdf.size, int(n_samples),
+                                   int(iterations), _ptr(key), C.byref(p), int(chunk_draws), _ptr(out)))
+        return out, int(p.value)
+
+    def bbn_ks_sim_dev(self, d_words, d_draw_cdf, d_model_cdf, sim_limit, n_samples, iterations, d_ks_sim, d_ws,
+                       ws_bytes, stream=0):
+        check(lib().pgx_bbn_ks_sim_dev(self._h, d_words, d_draw_cdf, d_model_cdf, int(sim_limit), int(n_samples),
+                                       int(iterations), d_ks_sim, d_ws, int(ws_bytes), stream))
+
+    def bbn_draws(self, draw_cdf, size, key, pos, chunk_draws=0):
+        """(values int64[size], pos): searchsorted(draw_cdf, random_sample(size), side='right') from the legacy
+        generator state (key advanced IN PLACE)."""
+        draw_cdf, key, p = _bbn_args(draw_cdf, key, pos)
+        out = np.empty(int(size), dtype=np.int64)
+        check(lib().pgx_bbn_draws(self._h, _ptr(draw_cdf), draw_cdf.size, int(size), _ptr(key), C.byref(p),
+                                  int(chunk_draws), _ptr(out)))
+        return out, int(p.value)
 
     def pan_core(self, bits, n_genes, perms):
         perms = np.ascontiguousarray(perms, dtype=np.int32)

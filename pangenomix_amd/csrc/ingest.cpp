@@ -861,6 +861,42 @@ int pgx_legacy_shuffles(uint32_t *key, int32_t *pos, uint32_t n, uint32_t n_iter
     return guarded("pgx_legacy_shuffles", [&] { return pgx_legacy_shuffles_impl(key, pos, n, n_iter, out_perms); });
 }
 
+// The generator's raw outputs in the order numpy consumes them (mt19937_next: twist when pos == 624, then the tempered
+// key[pos++]). Whole blocks go through mt_block straight into `out`; numpy twists lazily, so a stream that ends on a
+// block boundary leaves pos = 624 and the key un-twisted, as here. Each legacy random_sample() double takes two words.
+static int pgx_legacy_uniform_words_impl(uint32_t *key, int32_t *pos, uint64_t n_words, uint32_t *out) {
+    if (!key || !pos || (n_words && !out) || *pos < 0 || *pos > 624) {
+        pgx_set_error("pgx_legacy_uniform_words: invalid argument");
+        return PGX_ERR_INVALID;
+    }
+    uint64_t done = 0;
+    uint32_t p = (uint32_t)*pos;
+    while (done < n_words) {
+        if (p == 624) {
+            if (n_words - done >= 624) { mt_block(key, out + done); done += 624; continue; }
+            uint32_t tail[624];
+            mt_block(key, tail);
+            std::memcpy(out + done, tail, (size_t)(n_words - done) * 4);
+            p = (uint32_t)(n_words - done);
+            done = n_words;
+            break;
+        }
+        const uint64_t take = std::min<uint64_t>(624 - p, n_words - done);
+        for (uint64_t k = 0; k < take; ++k) {
+            uint32_t y = key[p + k];
+            y ^= y >> 11; y ^= (y << 7) & 0x9d2c5680u; y ^= (y << 15) & 0xefc60000u; y ^= y >> 18;
+            out[done + k] = y;
+        }
+        p += (uint32_t)take;
+        done += take;
+    }
+    *pos = (int32_t)p;
+    return PGX_OK;
+}
+int pgx_legacy_uniform_words(uint32_t *key, int32_t *pos, uint64_t n_words, uint32_t *out) {
+    return guarded("pgx_legacy_uniform_words", [&] { return pgx_legacy_uniform_words_impl(key, pos, n_words, out); });
+}
+
 // Feature names as fixed-width, zero-padded ASCII records (numpy dtype 'S<width>'):
 // <prefix><cluster[i]>            (variant == NULL: gene names)
 // <prefix><cluster[i]><variant><member[i]>   (allele names), reference pangenome.py:1944-1969.
