@@ -337,16 +337,10 @@ int pgx_legacy_shuffles(uint32_t *key, int32_t *pos, uint32_t n, uint32_t n_iter
  * a stream that ends on a block boundary leaves pos = 624 and the key un-twisted. Host only. */
 int pgx_legacy_uniform_words(uint32_t *key, int32_t *pos, uint64_t n_words, uint32_t *out);
 
-/* pgx_legacy_shuffles + pgx_pan_core_coo in one call (pangenome_analysis.py:51-98 from the binary table's
- * coordinates and the generator state): the draws are made on a host thread while the coordinates are uploaded and
- * the bitmap is built. out_perms: [n_iter][n_genomes], the permutations that were used. */
-int pgx_pan_core_coo_rng(pgx_ctx *ctx, const int32_t *rows, const int32_t *genomes, uint64_t n_records,
-                         uint32_t n_genes, uint32_t n_genomes, uint32_t *mt_key, int32_t *mt_pos, uint32_t n_iter,
-                         int32_t *out_perms, int32_t *out_pan, int32_t *out_core, uint64_t *out_duplicates);
-
 /* The whole of estimate_pan_core_size() (pangenome_analysis.py:51-98) from the gene x genome table's COO arrays:
  * `values` (the table's stored values, int64; may be NULL) are checked to be all 1 (out_not_one = how many are
- * not; the curves are then NOT computed), the permutations are drawn from the generator state, and the result is
+ * not; the curves are then NOT computed), the permutations are drawn from the generator state (as pgx_legacy_shuffles
+ * draws them, on a host thread while the coordinates are uploaded and the bitmap is built), and the result is
  * written as the reference returns it: out_table float64 [n_iter][2 * n_genomes], pan curves in columns
  * 0..n_genomes-1, core curves behind them. out_perms [n_iter][n_genomes] receives the permutations used. */
 int pgx_pan_core_table(pgx_ctx *ctx, const int32_t *rows, const int32_t *genomes, const int64_t *values,

@@ -81,8 +81,6 @@ SIGNATURES = {
     'pgx_fasta_write_consolidated': (C.c_int, [_P, _S, _S, _S]),
     'pgx_legacy_shuffles': (C.c_int, [_P, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, _P]),
     'pgx_legacy_uniform_words': (C.c_int, [_P, C.POINTER(C.c_int32), C.c_uint64, _P]),
-    'pgx_pan_core_coo_rng': (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint32, C.c_uint32, _P, C.POINTER(C.c_int32), C.c_uint32,
-                                      _P, _P, _P, C.POINTER(C.c_uint64)]),
     'pgx_pan_core_table': (C.c_int, [_P, _P, _P, _P, C.c_uint64, C.c_uint32, C.c_uint32, _P, C.POINTER(C.c_int32), C.c_uint32,
                                     _P, _P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     'pgx_bitmap_from_clusters': (C.c_int, [_P, _P, C.c_uint64, _P, _P, C.c_uint64, _P, C.c_uint32, C.c_uint32, C.c_uint32,
@@ -252,6 +250,14 @@ def _bbn_args(draw_cdf, key, pos):
     return draw_cdf, _legacy_key(key), C.c_int32(int(pos))
 
 
+def _coo_args(rows, genomes):
+    rows = np.ascontiguousarray(rows, dtype=np.int32)
+    genomes = np.ascontiguousarray(genomes, dtype=np.int32)
+    if rows.shape != genomes.shape or rows.ndim != 1:
+        raise ValueError('rows and genomes must be 1-D arrays of equal length')
+    return rows, genomes
+
+
 class Context(object):
     """Owns a pgx_ctx (device state). One per thread; not re-entrant."""
 
@@ -332,10 +338,7 @@ class Context(object):
 
     # -- K3 ----------------------------------------------------------------
     def presence_bitmap(self, rows, genomes, n_rows, n_genomes, return_duplicates=False):
-        rows = np.ascontiguousarray(rows, dtype=np.int32)
-        genomes = np.ascontiguousarray(genomes, dtype=np.int32)
-        if rows.shape != genomes.shape or rows.ndim != 1:
-            raise ValueError('rows and genomes must be 1-D arrays of equal length')
+        rows, genomes = _coo_args(rows, genomes)
         stride = lib().pgx_bitmap_stride_words(int(n_rows))
         bits = np.empty((int(n_genomes), stride), dtype=np.uint64)
         dup = C.c_uint64(0)
@@ -355,10 +358,7 @@ class Context(object):
 
     def row_counts(self, rows, genomes, n_rows, n_genomes):
         """(counts int32[n_rows], duplicates): genomes per row, from the device bitmap."""
-        rows = np.ascontiguousarray(rows, dtype=np.int32)
-        genomes = np.ascontiguousarray(genomes, dtype=np.int32)
-        if rows.shape != genomes.shape or rows.ndim != 1:
-            raise ValueError('rows and genomes must be 1-D arrays of equal length')
+        rows, genomes = _coo_args(rows, genomes)
         counts = np.empty(int(n_rows), dtype=np.int32)
         dup = C.c_uint64(0)
         check(lib().pgx_row_counts(self._h, _ptr(rows), _ptr(genomes), rows.size, int(n_rows), int(n_genomes),
@@ -367,11 +367,8 @@ class Context(object):
 
     def pan_core_coo(self, rows, genomes, n_genes, n_genomes, perms):
         """(pan, core, duplicates): bitmap built and consumed on the device in one call."""
-        rows = np.ascontiguousarray(rows, dtype=np.int32)
-        genomes = np.ascontiguousarray(genomes, dtype=np.int32)
+        rows, genomes = _coo_args(rows, genomes)
         perms = np.ascontiguousarray(perms, dtype=np.int32)
-        if rows.shape != genomes.shape or rows.ndim != 1:
-            raise ValueError('rows and genomes must be 1-D arrays of equal length')
         n_iter = perms.shape[0]
         if perms.ndim != 2 or perms.shape[1] != int(n_genomes):
             raise ValueError('perms must be [n_iter, n_genomes]')
@@ -382,30 +379,11 @@ class Context(object):
                                      _ptr(perms), n_iter, _ptr(pan), _ptr(core), C.byref(dup)))
         return pan, core, int(dup.value)
 
-    def pan_core_coo_rng(self, rows, genomes, n_genes, n_genomes, n_iter, mt_key, mt_pos):
-        """(pan, core, duplicates, perms, new_pos): as pan_core_coo, with the permutations drawn by the library from the
-        legacy generator's state (`mt_key` uint32[624], advanced in place; `mt_pos`) beside the upload."""
-        rows = np.ascontiguousarray(rows, dtype=np.int32)
-        genomes = np.ascontiguousarray(genomes, dtype=np.int32)
-        if rows.shape != genomes.shape or rows.ndim != 1:
-            raise ValueError('rows and genomes must be 1-D arrays of equal length')
-        perms = np.empty((int(n_iter), int(n_genomes)), dtype=np.int32)
-        pan = np.empty((int(n_iter), int(n_genomes)), dtype=np.int32)
-        core = np.empty((int(n_iter), int(n_genomes)), dtype=np.int32)
-        dup, pos = C.c_uint64(0), C.c_int32(int(mt_pos))
-        check(lib().pgx_pan_core_coo_rng(self._h, _ptr(rows), _ptr(genomes), rows.size, int(n_genes), int(n_genomes),
-                                         _ptr(mt_key), C.byref(pos), int(n_iter), _ptr(perms), _ptr(pan), _ptr(core),
-                                         C.byref(dup)))
-        return pan, core, int(dup.value), perms, int(pos.value)
-
     def pan_core_table(self, rows, genomes, values, n_genes, n_genomes, n_iter, mt_key, mt_pos):
         """(table float64 [n_iter, 2 n_genomes], duplicates, values that are not 1, perms, new_pos): the whole of
         estimate_pan_core_size() in one library call (pgx.h: pgx_pan_core_table). `values`: the table's stored
         values as int64, or None."""
-        rows = np.ascontiguousarray(rows, dtype=np.int32)
-        genomes = np.ascontiguousarray(genomes, dtype=np.int32)
-        if rows.shape != genomes.shape or rows.ndim != 1:
-            raise ValueError('rows and genomes must be 1-D arrays of equal length')
+        rows, genomes = _coo_args(rows, genomes)
         if values is not None:
             values = np.ascontiguousarray(values, dtype=np.int64)
             if values.shape != rows.shape:
@@ -451,10 +429,7 @@ class Context(object):
     def bernoulli_load(self, rows, genomes, n_genes, n_genomes):
         """Upload the binary table's coordinates once; its bitmap stays in the context for bernoulli_eval().
         Returns the number of duplicate coordinates."""
-        rows = np.ascontiguousarray(rows, dtype=np.int32)
-        genomes = np.ascontiguousarray(genomes, dtype=np.int32)
-        if rows.shape != genomes.shape or rows.ndim != 1:
-            raise ValueError('rows and genomes must be 1-D arrays of equal length')
+        rows, genomes = _coo_args(rows, genomes)
         dup = C.c_uint64(0)
         check(lib().pgx_bernoulli_load(self._h, _ptr(rows), _ptr(genomes), rows.size, int(n_genes), int(n_genomes),
                                        C.byref(dup)))

@@ -324,25 +324,10 @@ int load_coo(pgx_ctx *ctx, const int32_t *rows, const int32_t *genomes, uint64_t
     PGX_REQUIRE((uint64_t)G + S < (1ull << 31), "table too large");
     PGX_HIP(hipSetDevice(ctx->device_id));
     ctx->bern_loaded = false;
-    const size_t nbits = (size_t)S * pgx_bitmap_stride_words(G) * 8;
-    BnBuf d_rows(ctx, BN_SLOT_ROWS), d_genomes(ctx, BN_SLOT_GENOMES), d_bits(ctx, BN_SLOT_BITS), d_cnt(ctx, BN_SLOT_CNT);
-    PGX_HIP(d_rows.alloc(n_records * 4));
-    PGX_HIP(d_genomes.alloc(n_records * 4));
-    PGX_HIP(d_bits.alloc(nbits));
-    PGX_HIP(d_cnt.alloc(16));
-    if (n_records) {
-        int rc = pgx_staged_h2d(ctx, d_rows.p, rows, n_records * 4, ctx->stream);
-        if (rc == PGX_OK) rc = pgx_staged_h2d(ctx, d_genomes.p, genomes, n_records * 4, ctx->stream);
-        if (rc != PGX_OK) return rc;
-    }
-    int rc = pgx_presence_bitmap_dev(ctx, d_rows.as<int32_t>(), d_genomes.as<int32_t>(), n_records, G, S,
-                                     d_bits.as<uint64_t>(), d_cnt.as<uint64_t>(), ctx->stream);
+    BnBuf d_bits(ctx, BN_SLOT_BITS), d_cnt(ctx, BN_SLOT_CNT);
+    int rc = pgx_upload_and_build_bitmap(ctx, rows, genomes, n_records, G, S, BN_SLOT_ROWS, BN_SLOT_GENOMES, d_bits, d_cnt);
+    if (rc == PGX_OK) rc = pgx_read_record_counters(ctx, d_cnt, out_duplicates);
     if (rc != PGX_OK) return rc;
-    uint64_t cnt[2] = {0, 0};
-    PGX_HIP(hipMemcpyAsync(cnt, d_cnt.p, 16, hipMemcpyDeviceToHost, ctx->stream));
-    PGX_HIP(hipStreamSynchronize(ctx->stream));
-    PGX_REQUIRE(cnt[1] == 0, "record with row or genome index out of range");
-    if (out_duplicates) *out_duplicates = cnt[0];
     ctx->bern_genes = G;
     ctx->bern_genomes = S;
     ctx->bern_loaded = true;
@@ -402,23 +387,6 @@ int eval_loaded(pgx_ctx *ctx, const double *pq, uint32_t flags, double *out) {
     return PGX_OK;
 }
 
-// no C++ exception crosses the ABI (pgx.h)
-template <typename F>
-int barrier(const char *fn, F &&body) {
-    try {
-        return body();
-    } catch (const std::bad_alloc &) {
-        pgx_set_error("%s: out of host memory", fn);
-        return PGX_ERR_NOMEM;
-    } catch (const std::exception &e) {
-        pgx_set_error("%s: %s", fn, e.what());
-        return PGX_ERR_INTERNAL;
-    } catch (...) {
-        pgx_set_error("%s: unexpected exception", fn);
-        return PGX_ERR_INTERNAL;
-    }
-}
-
 }  // namespace
 
 extern "C" {
@@ -433,23 +401,23 @@ size_t pgx_bernoulli_workspace_bytes(uint32_t n_genes, uint32_t n_genomes) {
 
 int pgx_bernoulli_eval_dev(pgx_ctx *ctx, const uint64_t *d_bits, uint32_t n_genes, uint32_t n_genomes, const double *d_pq,
                            uint32_t flags, double *d_out, void *d_workspace, size_t workspace_bytes, void *stream) {
-    return barrier(__func__, [&] {
+    return guarded(__func__, [&] {
         return eval_dev(ctx, d_bits, n_genes, n_genomes, d_pq, flags, d_out, d_workspace, workspace_bytes, stream);
     });
 }
 
 int pgx_bernoulli_load(pgx_ctx *ctx, const int32_t *rows, const int32_t *genomes, uint64_t n_records, uint32_t n_genes,
                        uint32_t n_genomes, uint64_t *out_duplicates) {
-    return barrier(__func__, [&] { return load_coo(ctx, rows, genomes, n_records, n_genes, n_genomes, out_duplicates); });
+    return guarded(__func__, [&] { return load_coo(ctx, rows, genomes, n_records, n_genes, n_genomes, out_duplicates); });
 }
 
 int pgx_bernoulli_load_resident(pgx_ctx *ctx, uint64_t token, const int32_t *row_map, uint32_t n_genes,
                                 uint32_t n_genomes) {
-    return barrier(__func__, [&] { return load_resident(ctx, token, row_map, n_genes, n_genomes); });
+    return guarded(__func__, [&] { return load_resident(ctx, token, row_map, n_genes, n_genomes); });
 }
 
 int pgx_bernoulli_eval(pgx_ctx *ctx, const double *pq, uint32_t flags, double *out) {
-    return barrier(__func__, [&] { return eval_loaded(ctx, pq, flags, out); });
+    return guarded(__func__, [&] { return eval_loaded(ctx, pq, flags, out); });
 }
 
 }  // extern "C"

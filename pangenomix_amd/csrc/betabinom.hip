@@ -255,23 +255,6 @@ int draws_host(pgx_ctx *ctx, const double *draw_cdf, uint32_t L, uint64_t size, 
     return PGX_OK;
 }
 
-// no C++ exception crosses the ABI (pgx.h)
-template <typename F>
-int barrier(const char *fn, F &&body) {
-    try {
-        return body();
-    } catch (const std::bad_alloc &) {
-        pgx_set_error("%s: out of host memory", fn);
-        return PGX_ERR_NOMEM;
-    } catch (const std::exception &e) {
-        pgx_set_error("%s: %s", fn, e.what());
-        return PGX_ERR_INTERNAL;
-    } catch (...) {
-        pgx_set_error("%s: unexpected exception", fn);
-        return PGX_ERR_INTERNAL;
-    }
-}
-
 }  // namespace
 
 extern "C" {
@@ -281,7 +264,7 @@ size_t pgx_bbn_workspace_bytes(uint32_t sim_limit, uint32_t iterations) { return
 int pgx_bbn_ks_sim_dev(pgx_ctx *ctx, const uint32_t *d_words, const double *d_draw_cdf, const double *d_model_cdf,
                        uint32_t sim_limit, uint32_t n_samples, uint32_t iterations, double *d_ks_sim, void *d_workspace,
                        size_t workspace_bytes, void *stream) {
-    return barrier(__func__, [&] {
+    return guarded(__func__, [&] {
         return ks_dev(ctx, d_words, d_draw_cdf, d_model_cdf, sim_limit, n_samples, iterations, d_ks_sim, d_workspace,
                       workspace_bytes, static_cast<hipStream_t>(stream));
     });
@@ -289,14 +272,14 @@ int pgx_bbn_ks_sim_dev(pgx_ctx *ctx, const uint32_t *d_words, const double *d_dr
 
 int pgx_bbn_ks_sim(pgx_ctx *ctx, const double *draw_cdf, const double *model_cdf, uint32_t sim_limit, uint32_t n_samples,
                    uint32_t iterations, uint32_t *mt_key, int32_t *mt_pos, uint64_t chunk_draws, double *out_ks_sim) {
-    return barrier(__func__, [&] {
+    return guarded(__func__, [&] {
         return ks_host(ctx, draw_cdf, model_cdf, sim_limit, n_samples, iterations, mt_key, mt_pos, chunk_draws, out_ks_sim);
     });
 }
 
 int pgx_bbn_draws(pgx_ctx *ctx, const double *draw_cdf, uint32_t sim_limit, uint64_t size, uint32_t *mt_key,
                   int32_t *mt_pos, uint64_t chunk_draws, int64_t *out_idx) {
-    return barrier(__func__, [&] { return draws_host(ctx, draw_cdf, sim_limit, size, mt_key, mt_pos, chunk_draws, out_idx); });
+    return guarded(__func__, [&] { return draws_host(ctx, draw_cdf, sim_limit, size, mt_key, mt_pos, chunk_draws, out_idx); });
 }
 
 }  // extern "C"

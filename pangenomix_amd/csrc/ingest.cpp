@@ -36,9 +36,7 @@
 #include <thread>
 #include <vector>
 
-#include "../../include/pgx.h"
-
-void pgx_set_error(const char *fmt, ...);
+#include "pgx_guard.h"
 
 namespace {
 
@@ -254,15 +252,6 @@ void parallel_for(size_t n, int threads, F f) {
     for (auto &th : pool) th.join();
     if (failed == 1) throw std::bad_alloc();
     if (failed) throw std::runtime_error("a worker thread failed");
-}
-
-// Every entry point of the C ABI that allocates runs inside this guard: no exception crosses the boundary (pgx.h).
-template <typename F>
-int guarded(const char *fn, F body) {
-    try { return body(); }
-    catch (const std::bad_alloc &) { pgx_set_error("%s: out of host memory", fn); return PGX_ERR_NOMEM; }
-    catch (const std::exception &e) { pgx_set_error("%s: %s", fn, e.what()); return PGX_ERR_INTERNAL; }
-    catch (...) { pgx_set_error("%s: unexpected exception", fn); return PGX_ERR_INTERNAL; }
 }
 
 struct Out {   // buffered file writer

@@ -299,8 +299,47 @@ struct PcBuf : DevBuf {
     PcBuf(pgx_ctx *c, int s) { ctx = c; slot = s; }
 };
 
+// Host threads that run beside an entry point's own work: whatever was started is joined at the end of the scope on
+// every way out of it, an exception from starting a further thread included (destroying a joinable std::thread is
+// std::terminate). Declare it AFTER everything the threads refer to.
+struct JoinedThreads {
+    std::vector<std::thread> v;
+    ~JoinedThreads() { for (auto &th : v) th.join(); }
+};
+
 }  // namespace
 
+// ---- shared with bernoulli.hip (pgx_internal.h) -------------------------------------------------------------------
+int pgx_upload_and_build_bitmap(pgx_ctx *ctx, const int32_t *rows, const int32_t *genomes, uint64_t n_records,
+                                uint32_t n_rows, uint32_t n_genomes, int slot_rows, int slot_genomes, DevBuf &d_bits,
+                                DevBuf &d_cnt) {
+    const size_t nbits = (size_t)n_genomes * pgx_bitmap_stride_words(n_rows) * 8;
+    PcBuf d_rows(ctx, slot_rows), d_genomes(ctx, slot_genomes);
+    PGX_HIP(d_rows.alloc(n_records * 4));
+    PGX_HIP(d_genomes.alloc(n_records * 4));
+    PGX_HIP(d_bits.alloc(nbits));
+    PGX_HIP(d_cnt.alloc(16));
+    if (n_records) {
+        int rc = pgx_staged_h2d(ctx, d_rows.p, rows, n_records * 4, ctx->stream);
+        if (rc == PGX_OK) rc = pgx_staged_h2d(ctx, d_genomes.p, genomes, n_records * 4, ctx->stream);
+        if (rc != PGX_OK) return rc;
+    }
+    return pgx_presence_bitmap_dev(ctx, d_rows.as<int32_t>(), d_genomes.as<int32_t>(), n_records, n_rows, n_genomes,
+                                   d_bits.as<uint64_t>(), d_cnt.as<uint64_t>(), ctx->stream);
+}
+
+int pgx_read_record_counters(pgx_ctx *ctx, DevBuf &d_cnt, uint64_t *out_duplicates) {
+    uint64_t cnt[2] = {0, 0};
+    PGX_HIP(hipMemcpyAsync(cnt, d_cnt.p, 16, hipMemcpyDeviceToHost, ctx->stream));
+    PGX_HIP(hipStreamSynchronize(ctx->stream));
+    PGX_REQUIRE(cnt[1] == 0, "record with row or genome index out of range");
+    if (out_duplicates) *out_duplicates = cnt[0];
+    return PGX_OK;
+}
+
+// ---- the C ABI. DevBuf and ProfScope grow vectors of the context and pgx_pan_core_table starts threads, so every entry
+// point below that uses one of them is a function-try-block whose handler hands the exception in flight to the guard
+// (pgx_guard.h): nothing crosses the ABI, and PGX_REQUIRE's messages keep the entry point's own name.
 extern "C" {
 
 uint32_t pgx_bitmap_stride_words(uint32_t n_genes) {
@@ -316,7 +355,7 @@ size_t pgx_pan_core_workspace_bytes(uint32_t n_genes, uint32_t n_genomes, uint32
 
 int pgx_presence_bitmap_dev(pgx_ctx *ctx, const int32_t *d_rows, const int32_t *d_genomes,
                             uint64_t n_records, uint32_t n_rows, uint32_t n_genomes,
-                            uint64_t *d_out_bits, uint64_t *d_counters, void *stream_) {
+                            uint64_t *d_out_bits, uint64_t *d_counters, void *stream_) try {
     PGX_REQUIRE(ctx && d_out_bits, "NULL argument");
     PGX_REQUIRE(n_records == 0 || (d_rows && d_genomes), "NULL record arrays");
     hipStream_t stream = (hipStream_t)stream_;
@@ -335,47 +374,44 @@ int pgx_presence_bitmap_dev(pgx_ctx *ctx, const int32_t *d_rows, const int32_t *
     }
     PGX_HIP(hipGetLastError());
     return PGX_OK;
-}
-
-// uploads the records, builds the bitmap on the device; counters (device, 2 x u64) are left for the caller
-static int upload_and_build_bitmap(pgx_ctx *ctx, const int32_t *rows, const int32_t *genomes, uint64_t n_records,
-                                   uint32_t n_rows, uint32_t n_genomes, DevBuf &d_bits, DevBuf &d_cnt) {
-    const size_t nbits = (size_t)n_genomes * pgx_bitmap_stride_words(n_rows) * 8;
-    PcBuf d_rows(ctx, PC_SLOT_ROWS), d_genomes(ctx, PC_SLOT_GENOMES);
-    PGX_HIP(d_rows.alloc(n_records * 4));
-    PGX_HIP(d_genomes.alloc(n_records * 4));
-    PGX_HIP(d_bits.alloc(nbits));
-    PGX_HIP(d_cnt.alloc(16));
-    if (n_records) {
-        int rc = pgx_staged_h2d(ctx, d_rows.p, rows, n_records * 4, ctx->stream);
-        if (rc == PGX_OK) rc = pgx_staged_h2d(ctx, d_genomes.p, genomes, n_records * 4, ctx->stream);
-        if (rc != PGX_OK) return rc;
-    }
-    return pgx_presence_bitmap_dev(ctx, d_rows.as<int32_t>(), d_genomes.as<int32_t>(), n_records, n_rows,
-                                   n_genomes, d_bits.as<uint64_t>(), d_cnt.as<uint64_t>(), ctx->stream);
-}
+} catch (...) { return guarded_catch(__func__); }
 
 int pgx_presence_bitmap(pgx_ctx *ctx, const int32_t *rows, const int32_t *genomes, uint64_t n_records,
-                        uint32_t n_rows, uint32_t n_genomes, uint64_t *out_bits, uint64_t *out_duplicates) {
+                        uint32_t n_rows, uint32_t n_genomes, uint64_t *out_bits, uint64_t *out_duplicates) try {
     PGX_REQUIRE(ctx && out_bits, "NULL argument");
     PGX_REQUIRE(n_records == 0 || (rows && genomes), "NULL record arrays");
     PGX_HIP(hipSetDevice(ctx->device_id));
     const size_t nbits = (size_t)n_genomes * pgx_bitmap_stride_words(n_rows) * 8;
     PcBuf d_bits(ctx, PC_SLOT_BITS), d_cnt(ctx, PC_SLOT_CNT);
-    int rc = upload_and_build_bitmap(ctx, rows, genomes, n_records, n_rows, n_genomes, d_bits, d_cnt);
+    int rc = pgx_upload_and_build_bitmap(ctx, rows, genomes, n_records, n_rows, n_genomes, PC_SLOT_ROWS, PC_SLOT_GENOMES,
+                                         d_bits, d_cnt);
     if (rc != PGX_OK) return rc;
-    uint64_t cnt[2] = {0, 0};
     if (nbits) PGX_HIP(hipMemcpyAsync(out_bits, d_bits.p, nbits, hipMemcpyDeviceToHost, ctx->stream));
-    PGX_HIP(hipMemcpyAsync(cnt, d_cnt.p, 16, hipMemcpyDeviceToHost, ctx->stream));
-    PGX_HIP(hipStreamSynchronize(ctx->stream));
-    PGX_REQUIRE(cnt[1] == 0, "record with row or genome index out of range");
-    if (out_duplicates) *out_duplicates = cnt[0];
+    return pgx_read_record_counters(ctx, d_cnt, out_duplicates);
+} catch (...) { return guarded_catch(__func__); }
+
+// THE launch of the sweep: geometry, one item per (iteration, stripe, wave of the stripe), partial sums into d_ws
+// (pgx_pan_core_workspace_bytes); *n_partials = how many the reduce kernel that follows has to add up.
+static int launch_sweep(pgx_ctx *ctx, const uint64_t *d_bits, uint32_t n_genes, uint32_t n_genomes, const int32_t *d_perms,
+                        uint32_t n_iter, void *d_ws, hipStream_t stream, uint32_t *n_partials) {
+    const PanCoreGeom g = make_geom(n_genes, n_genomes);
+    const uint64_t items = (uint64_t)n_iter * g.wps;  // per stripe
+    const uint64_t blocks = ((items + PC_WAVES - 1) / PC_WAVES) * g.stripes;
+    PGX_REQUIRE(blocks < (1ull << 31), "problem too large for one launch");
+    {
+        ProfScope prof(ctx, "pan_core_sweep_kernel", stream);
+        pan_core_sweep_kernel<<<(uint32_t)blocks, PC_WAVES * 64, 0, stream>>>(
+            (const uint4 *)d_bits, g.stride * 8, d_perms, n_iter, n_genomes, g.Ls, g.wps, g.Lw, g.stripes,
+            (uint32_t *)d_ws);
+    }
+    PGX_HIP(hipGetLastError());
+    *n_partials = g.partials;
     return PGX_OK;
 }
 
 int pgx_pan_core_dev(pgx_ctx *ctx, const uint64_t *d_bits, uint32_t n_genes, uint32_t n_genomes,
                      const int32_t *d_perms, uint32_t n_iter, int32_t *d_out_pan, int32_t *d_out_core,
-                     void *d_workspace, size_t workspace_bytes, void *stream_) {
+                     void *d_workspace, size_t workspace_bytes, void *stream_) try {
     PGX_REQUIRE(ctx, "NULL context");
     if (n_iter == 0 || n_genomes == 0) return PGX_OK;
     PGX_REQUIRE(d_bits && d_perms && d_out_pan && d_out_core && d_workspace, "NULL argument");
@@ -383,18 +419,9 @@ int pgx_pan_core_dev(pgx_ctx *ctx, const uint64_t *d_bits, uint32_t n_genes, uin
                 "workspace too small (see pgx_pan_core_workspace_bytes)");
     PGX_REQUIRE(((uintptr_t)d_bits & 15u) == 0, "bitmap must be 16-byte aligned");
     hipStream_t stream = (hipStream_t)stream_;
-    const PanCoreGeom g = make_geom(n_genes, n_genomes);
-    const uint32_t n_partials = g.partials;
-    {
-        const uint64_t items = (uint64_t)n_iter * g.wps;  // per stripe
-        const uint64_t blocks = ((items + PC_WAVES - 1) / PC_WAVES) * g.stripes;
-        PGX_REQUIRE(blocks < (1ull << 31), "problem too large for one launch");
-        ProfScope prof(ctx, "pan_core_sweep_kernel", stream);
-        pan_core_sweep_kernel<<<(uint32_t)blocks, PC_WAVES * 64, 0, stream>>>(
-            (const uint4 *)d_bits, g.stride * 8, d_perms, n_iter, n_genomes, g.Ls, g.wps, g.Lw, g.stripes,
-            (uint32_t *)d_workspace);
-    }
-    PGX_HIP(hipGetLastError());
+    uint32_t n_partials = 0;
+    int rc = launch_sweep(ctx, d_bits, n_genes, n_genomes, d_perms, n_iter, d_workspace, stream, &n_partials);
+    if (rc != PGX_OK) return rc;
     const size_t n_out = (size_t)n_iter * n_genomes;
     const size_t want = (n_out + 255) / 256;
     {
@@ -404,7 +431,7 @@ int pgx_pan_core_dev(pgx_ctx *ctx, const uint64_t *d_bits, uint32_t n_genes, uin
     }
     PGX_HIP(hipGetLastError());
     return PGX_OK;
-}
+} catch (...) { return guarded_catch(__func__); }
 
 // bitmap already on the device (d_bits): permutations up, curves down
 static int pan_core_from_device_bitmap(pgx_ctx *ctx, const uint64_t *d_bits, uint32_t n_genes, uint32_t n_genomes,
@@ -428,7 +455,7 @@ static int pan_core_from_device_bitmap(pgx_ctx *ctx, const uint64_t *d_bits, uin
 }
 
 int pgx_pan_core(pgx_ctx *ctx, const uint64_t *bits, uint32_t n_genes, uint32_t n_genomes,
-                 const int32_t *perms, uint32_t n_iter, int32_t *out_pan, int32_t *out_core) {
+                 const int32_t *perms, uint32_t n_iter, int32_t *out_pan, int32_t *out_core) try {
     PGX_REQUIRE(ctx, "NULL context");
     if (n_iter == 0 || n_genomes == 0) return PGX_OK;
     PGX_REQUIRE(bits && perms && out_pan && out_core, "NULL argument");
@@ -441,146 +468,106 @@ int pgx_pan_core(pgx_ctx *ctx, const uint64_t *bits, uint32_t n_genes, uint32_t 
     if (rc != PGX_OK) return rc;
     PGX_HIP(hipStreamSynchronize(ctx->stream));
     return PGX_OK;
-}
+} catch (...) { return guarded_catch(__func__); }
 
 int pgx_pan_core_coo(pgx_ctx *ctx, const int32_t *rows, const int32_t *genomes, uint64_t n_records,
                      uint32_t n_genes, uint32_t n_genomes, const int32_t *perms, uint32_t n_iter,
-                     int32_t *out_pan, int32_t *out_core, uint64_t *out_duplicates) {
+                     int32_t *out_pan, int32_t *out_core, uint64_t *out_duplicates) try {
     PGX_REQUIRE(ctx, "NULL context");
     PGX_REQUIRE(n_records == 0 || (rows && genomes), "NULL record arrays");
     PGX_REQUIRE(n_iter == 0 || n_genomes == 0 || (perms && out_pan && out_core), "NULL argument");
     PGX_HIP(hipSetDevice(ctx->device_id));
     PcBuf d_bits(ctx, PC_SLOT_BITS), d_cnt(ctx, PC_SLOT_CNT);
-    int rc = upload_and_build_bitmap(ctx, rows, genomes, n_records, n_genes, n_genomes, d_bits, d_cnt);
+    int rc = pgx_upload_and_build_bitmap(ctx, rows, genomes, n_records, n_genes, n_genomes, PC_SLOT_ROWS, PC_SLOT_GENOMES,
+                                         d_bits, d_cnt);
     if (rc != PGX_OK) return rc;
     if (n_iter && n_genomes) {
         rc = pan_core_from_device_bitmap(ctx, d_bits.as<uint64_t>(), n_genes, n_genomes, perms, n_iter, out_pan, out_core);
         if (rc != PGX_OK) return rc;
     }
-    uint64_t cnt[2] = {0, 0};
-    PGX_HIP(hipMemcpyAsync(cnt, d_cnt.p, 16, hipMemcpyDeviceToHost, ctx->stream));
-    PGX_HIP(hipStreamSynchronize(ctx->stream));
-    PGX_REQUIRE(cnt[1] == 0, "record with row or genome index out of range");
-    if (out_duplicates) *out_duplicates = cnt[0];
-    return PGX_OK;
-}
+    return pgx_read_record_counters(ctx, d_cnt, out_duplicates);
+} catch (...) { return guarded_catch(__func__); }
 
-// estimate_pan_core_size() in one call: the permutations are drawn from the legacy generator's state on a host
-// thread WHILE the coordinates travel to the device and the bitmap is built there (3 ms of draws beside 2-3 ms of
-// copies for the 150,000 x 400 table), then they follow and the curves are computed.
-int pgx_pan_core_coo_rng(pgx_ctx *ctx, const int32_t *rows, const int32_t *genomes, uint64_t n_records,
-                         uint32_t n_genes, uint32_t n_genomes, uint32_t *mt_key, int32_t *mt_pos, uint32_t n_iter,
-                         int32_t *out_perms, int32_t *out_pan, int32_t *out_core, uint64_t *out_duplicates) {
-    PGX_REQUIRE(ctx, "NULL context");
-    PGX_REQUIRE(n_records == 0 || (rows && genomes), "NULL record arrays");
-    PGX_REQUIRE(mt_key && mt_pos, "NULL generator state");
-    PGX_REQUIRE(n_iter == 0 || n_genomes == 0 || (out_perms && out_pan && out_core), "NULL argument");
-    PGX_HIP(hipSetDevice(ctx->device_id));
-    int rc_draw = PGX_OK;
-    std::string draw_error;
-    std::thread draw([&]() {
-        rc_draw = pgx_legacy_shuffles(mt_key, mt_pos, n_genomes, n_iter, out_perms);
-        if (rc_draw != PGX_OK) draw_error = pgx_last_error();     // (the error text is thread-local)
-    });
-    PcBuf d_bits(ctx, PC_SLOT_BITS), d_cnt(ctx, PC_SLOT_CNT);
-    int rc = upload_and_build_bitmap(ctx, rows, genomes, n_records, n_genes, n_genomes, d_bits, d_cnt);
-    draw.join();
+// What the two table entry points share, from a bitmap on the device (d_bits) and permutations on the host: the
+// permutations up, the sweep, the partial sums reduced into the float64 table, the table down. Everything is enqueued
+// on ctx->stream; the caller synchronises.
+static int table_from_device_bitmap(pgx_ctx *ctx, const uint64_t *d_bits, uint32_t n_genes, uint32_t n_genomes,
+                                    const int32_t *perms, uint32_t n_iter, double *out_table) {
+    const size_t nperm = (size_t)n_iter * n_genomes * 4;
+    const size_t nws = pgx_pan_core_workspace_bytes(n_genes, n_genomes, n_iter);
+    PcBuf d_perms(ctx, PC_SLOT_PERMS), d_ws(ctx, PC_SLOT_WS), d_table(ctx, PC_SLOT_TABLE);
+    PGX_HIP(d_perms.alloc(nperm));
+    PGX_HIP(d_ws.alloc(nws));
+    PGX_HIP(d_table.alloc(nperm * 4));
+    PGX_HIP(hipMemcpyAsync(d_perms.p, perms, nperm, hipMemcpyHostToDevice, ctx->stream));
+    uint32_t n_partials = 0;
+    int rc = launch_sweep(ctx, d_bits, n_genes, n_genomes, d_perms.as<int32_t>(), n_iter, d_ws.p, ctx->stream, &n_partials);
     if (rc != PGX_OK) return rc;
-    if (rc_draw != PGX_OK) { pgx_set_error("%s", draw_error.c_str()); return rc_draw; }
-    if (n_iter && n_genomes) {
-        rc = pan_core_from_device_bitmap(ctx, d_bits.as<uint64_t>(), n_genes, n_genomes, out_perms, n_iter, out_pan, out_core);
-        if (rc != PGX_OK) return rc;
+    {
+        const size_t want = ((size_t)n_iter * n_genomes + 255) / 256;
+        ProfScope prof(ctx, "pan_core_reduce_kernel", ctx->stream);
+        pan_core_reduce_table_kernel<<<(uint32_t)(want < 2048 ? want : 2048), 256, 0, ctx->stream>>>(
+            d_ws.as<uint32_t>(), n_partials, n_iter, n_genomes, d_table.as<double>());
     }
-    uint64_t cnt[2] = {0, 0};
-    PGX_HIP(hipMemcpyAsync(cnt, d_cnt.p, 16, hipMemcpyDeviceToHost, ctx->stream));
-    PGX_HIP(hipStreamSynchronize(ctx->stream));
-    PGX_REQUIRE(cnt[1] == 0, "record with row or genome index out of range");
-    if (out_duplicates) *out_duplicates = cnt[0];
+    PGX_HIP(hipGetLastError());
+    PGX_HIP(hipMemcpyAsync(out_table, d_table.p, nperm * 4, hipMemcpyDeviceToHost, ctx->stream));
     return PGX_OK;
 }
 
 // estimate_pan_core_size() from the table's COO arrays to the float64 result in ONE call (pangenome_analysis.py:51-98):
 // on host threads, side by side -- the legacy-generator draws, the check that every stored value is 1, the staged
-// upload of the coordinates; on the device -- bitmap, curves, the [n_iter][2 S] float64 table; one copy down.
+// upload of the coordinates (3 ms of draws beside 2-3 ms of copies for the 150,000 x 400 table); on the device --
+// bitmap, curves, the [n_iter][2 S] float64 table; one copy down.
 int pgx_pan_core_table(pgx_ctx *ctx, const int32_t *rows, const int32_t *genomes, const int64_t *values,
                        uint64_t n_records, uint32_t n_genes, uint32_t n_genomes, uint32_t *mt_key, int32_t *mt_pos,
                        uint32_t n_iter, int32_t *out_perms, double *out_table, uint64_t *out_duplicates,
-                       uint64_t *out_not_one) {
+                       uint64_t *out_not_one) try {
     PGX_REQUIRE(ctx, "NULL context");
     PGX_REQUIRE(n_records == 0 || (rows && genomes), "NULL record arrays");
     PGX_REQUIRE(mt_key && mt_pos, "NULL generator state");
     PGX_REQUIRE(n_iter == 0 || n_genomes == 0 || (out_perms && out_table), "NULL argument");
     PGX_HIP(hipSetDevice(ctx->device_id));
     int rc_draw = PGX_OK;
-    std::string draw_error;
-    std::thread draw([&]() {
-        rc_draw = pgx_legacy_shuffles(mt_key, mt_pos, n_genomes, n_iter, out_perms);
-        if (rc_draw != PGX_OK) draw_error = pgx_last_error();     // (the error text is thread-local)
-    });
-    // every stored value must be 1 (the OR/AND form equals the reference's loop only for a 0/1 table): checked here,
-    // on a few threads, instead of by a 3 ms numpy pass before the call
-    uint64_t not_one = 0;
-    std::vector<std::thread> checkers;
-    std::vector<uint64_t> bad(4, 0);
-    if (values && n_records) {
-        const unsigned T = n_records < (1u << 20) ? 1u : 4u;
+    char draw_error[512] = "";
+    uint64_t bad[4] = {0, 0, 0, 0};
+    const unsigned T = !(values && n_records) ? 0u : n_records < (1u << 20) ? 1u : 4u;
+    PcBuf d_bits(ctx, PC_SLOT_BITS), d_cnt(ctx, PC_SLOT_CNT);
+    int rc;
+    {
+        JoinedThreads threads;
+        threads.v.reserve(1 + T);
+        threads.v.emplace_back([&]() {
+            rc_draw = pgx_legacy_shuffles(mt_key, mt_pos, n_genomes, n_iter, out_perms);
+            if (rc_draw != PGX_OK) snprintf(draw_error, sizeof(draw_error), "%s", pgx_last_error());  // (thread-local text)
+        });
+        // every stored value must be 1 (the OR/AND form equals the reference's loop only for a 0/1 table): checked
+        // here, on a few threads, instead of by a 3 ms numpy pass before the call
         for (unsigned t = 0; t < T; ++t)
-            checkers.emplace_back([&, t, T]() {
+            threads.v.emplace_back([&, t]() {
                 const uint64_t a = n_records * t / T, b = n_records * (t + 1) / T;
                 uint64_t c = 0;
                 for (uint64_t i = a; i < b; ++i) c += values[i] != 1;
                 bad[t] = c;
             });
-    }
-    PcBuf d_bits(ctx, PC_SLOT_BITS), d_cnt(ctx, PC_SLOT_CNT);
-    int rc = upload_and_build_bitmap(ctx, rows, genomes, n_records, n_genes, n_genomes, d_bits, d_cnt);
-    draw.join();
-    for (auto &th : checkers) th.join();
-    for (uint64_t c : bad) not_one += c;
+        rc = pgx_upload_and_build_bitmap(ctx, rows, genomes, n_records, n_genes, n_genomes, PC_SLOT_ROWS, PC_SLOT_GENOMES,
+                                         d_bits, d_cnt);
+    }   // (draws and checks are done)
+    const uint64_t not_one = bad[0] + bad[1] + bad[2] + bad[3];
     if (out_not_one) *out_not_one = not_one;
     if (rc != PGX_OK) return rc;
-    if (rc_draw != PGX_OK) { pgx_set_error("%s", draw_error.c_str()); return rc_draw; }
+    if (rc_draw != PGX_OK) { pgx_set_error("%s", draw_error); return rc_draw; }
     if (n_iter && n_genomes && !not_one) {
-        const size_t nperm = (size_t)n_iter * n_genomes * 4;
-        const size_t nws = pgx_pan_core_workspace_bytes(n_genes, n_genomes, n_iter);
-        PcBuf d_perms(ctx, PC_SLOT_PERMS), d_ws(ctx, PC_SLOT_WS), d_table(ctx, PC_SLOT_TABLE);
-        PGX_HIP(d_perms.alloc(nperm));
-        PGX_HIP(d_ws.alloc(nws));
-        PGX_HIP(d_table.alloc(nperm * 4));
-        PGX_HIP(hipMemcpyAsync(d_perms.p, out_perms, nperm, hipMemcpyHostToDevice, ctx->stream));
-        const PanCoreGeom g = make_geom(n_genes, n_genomes);
-        {
-            const uint64_t items = (uint64_t)n_iter * g.wps;  // per stripe
-            const uint64_t blocks = ((items + PC_WAVES - 1) / PC_WAVES) * g.stripes;
-            PGX_REQUIRE(blocks < (1ull << 31), "problem too large for one launch");
-            ProfScope prof(ctx, "pan_core_sweep_kernel", ctx->stream);
-            pan_core_sweep_kernel<<<(uint32_t)blocks, PC_WAVES * 64, 0, ctx->stream>>>(
-                d_bits.as<uint4>(), g.stride * 8, d_perms.as<int32_t>(), n_iter, n_genomes, g.Ls, g.wps, g.Lw, g.stripes,
-                d_ws.as<uint32_t>());
-        }
-        PGX_HIP(hipGetLastError());
-        {
-            const size_t want = ((size_t)n_iter * n_genomes + 255) / 256;
-            ProfScope prof(ctx, "pan_core_reduce_kernel", ctx->stream);
-            pan_core_reduce_table_kernel<<<(uint32_t)(want < 2048 ? want : 2048), 256, 0, ctx->stream>>>(
-                d_ws.as<uint32_t>(), g.partials, n_iter, n_genomes, d_table.as<double>());
-        }
-        PGX_HIP(hipGetLastError());
-        PGX_HIP(hipMemcpyAsync(out_table, d_table.p, nperm * 4, hipMemcpyDeviceToHost, ctx->stream));
+        rc = table_from_device_bitmap(ctx, d_bits.as<uint64_t>(), n_genes, n_genomes, out_perms, n_iter, out_table);
+        if (rc != PGX_OK) return rc;
     }
-    uint64_t cnt[2] = {0, 0};
-    PGX_HIP(hipMemcpyAsync(cnt, d_cnt.p, 16, hipMemcpyDeviceToHost, ctx->stream));
-    PGX_HIP(hipStreamSynchronize(ctx->stream));
-    PGX_REQUIRE(cnt[1] == 0, "record with row or genome index out of range");
-    if (out_duplicates) *out_duplicates = cnt[0];
-    return PGX_OK;
-}
+    return pgx_read_record_counters(ctx, d_cnt, out_duplicates);
+} catch (...) { return guarded_catch(__func__); }
 
 // ---- device-resident hand-off: clustering result -> bitmap (kept in the context) -> pan/core curves ---------------
 int pgx_bitmap_from_clusters(pgx_ctx *ctx, const int32_t *cluster_of_group, uint64_t n_groups,
                              const int32_t *group_of_record, const uint32_t *file_of_record, uint64_t n_records,
                              const int32_t *genome_of_file, uint32_t n_files, uint32_t n_genes, uint32_t n_genomes,
-                             uint64_t *out_token) {
+                             uint64_t *out_token) try {
     PGX_REQUIRE(ctx && out_token, "NULL argument");
     PGX_REQUIRE(n_records == 0 || (cluster_of_group && group_of_record && file_of_record && genome_of_file), "NULL arrays");
     PGX_REQUIRE(n_groups < (1ull << 31), "too many groups");
@@ -613,6 +600,7 @@ int pgx_bitmap_from_clusters(pgx_ctx *ctx, const int32_t *cluster_of_group, uint
             n_files, n_genes, n_genomes, stride, d_bits.as<unsigned long long>(), d_cnt.as<unsigned long long>());
         PGX_HIP(hipGetLastError());
     }
+    // (its own read-back: another message, and duplicates are not counted here)
     uint64_t cnt[2] = {0, 0};
     PGX_HIP(hipMemcpyAsync(cnt, d_cnt.p, 16, hipMemcpyDeviceToHost, st));
     PGX_HIP(hipStreamSynchronize(st));
@@ -621,9 +609,9 @@ int pgx_bitmap_from_clusters(pgx_ctx *ctx, const int32_t *cluster_of_group, uint
     ctx->resident_genes = n_genes; ctx->resident_genomes = n_genomes;
     *out_token = ctx->resident_token;
     return PGX_OK;
-}
+} catch (...) { return guarded_catch(__func__); }
 
-int pgx_bitmap_resident_read(pgx_ctx *ctx, uint64_t token, uint64_t *out_bits) {
+int pgx_bitmap_resident_read(pgx_ctx *ctx, uint64_t token, uint64_t *out_bits) try {
     PGX_REQUIRE(ctx && out_bits, "NULL argument");
     PGX_REQUIRE(token != 0 && token == ctx->resident_token, "the bitmap of that token is not resident any more");
     PGX_HIP(hipSetDevice(ctx->device_id));
@@ -633,10 +621,10 @@ int pgx_bitmap_resident_read(pgx_ctx *ctx, uint64_t token, uint64_t *out_bits) {
     PGX_HIP(hipMemcpyAsync(out_bits, d_bits.p, nbits, hipMemcpyDeviceToHost, ctx->stream));
     PGX_HIP(hipStreamSynchronize(ctx->stream));
     return PGX_OK;
-}
+} catch (...) { return guarded_catch(__func__); }
 
 int pgx_pan_core_table_resident(pgx_ctx *ctx, uint64_t token, uint32_t n_genes, uint32_t n_genomes, uint32_t *mt_key,
-                                int32_t *mt_pos, uint32_t n_iter, int32_t *out_perms, double *out_table) {
+                                int32_t *mt_pos, uint32_t n_iter, int32_t *out_perms, double *out_table) try {
     PGX_REQUIRE(ctx && mt_key && mt_pos, "NULL argument");
     PGX_REQUIRE(token != 0 && token == ctx->resident_token && n_genes == ctx->resident_genes && n_genomes == ctx->resident_genomes,
                 "the bitmap of that token is not resident any more");
@@ -645,39 +633,16 @@ int pgx_pan_core_table_resident(pgx_ctx *ctx, uint64_t token, uint32_t n_genes, 
     int rc = pgx_legacy_shuffles(mt_key, mt_pos, n_genomes, n_iter, out_perms);
     if (rc != PGX_OK) return rc;
     if (n_iter == 0 || n_genomes == 0) return PGX_OK;
-    const size_t nperm = (size_t)n_iter * n_genomes * 4;
-    const size_t nws = pgx_pan_core_workspace_bytes(n_genes, n_genomes, n_iter);
-    PcBuf d_bits(ctx, PC_SLOT_RESIDENT), d_perms(ctx, PC_SLOT_PERMS), d_ws(ctx, PC_SLOT_WS), d_table(ctx, PC_SLOT_TABLE);
+    PcBuf d_bits(ctx, PC_SLOT_RESIDENT);
     PGX_HIP(d_bits.alloc((size_t)n_genomes * pgx_bitmap_stride_words(n_genes) * 8));   // (a view of the slot)
-    PGX_HIP(d_perms.alloc(nperm));
-    PGX_HIP(d_ws.alloc(nws));
-    PGX_HIP(d_table.alloc(nperm * 4));
-    PGX_HIP(hipMemcpyAsync(d_perms.p, out_perms, nperm, hipMemcpyHostToDevice, ctx->stream));
-    const PanCoreGeom g = make_geom(n_genes, n_genomes);
-    {
-        const uint64_t items = (uint64_t)n_iter * g.wps;
-        const uint64_t blocks = ((items + PC_WAVES - 1) / PC_WAVES) * g.stripes;
-        PGX_REQUIRE(blocks < (1ull << 31), "problem too large for one launch");
-        ProfScope prof(ctx, "pan_core_sweep_kernel", ctx->stream);
-        pan_core_sweep_kernel<<<(uint32_t)blocks, PC_WAVES * 64, 0, ctx->stream>>>(
-            d_bits.as<uint4>(), g.stride * 8, d_perms.as<int32_t>(), n_iter, n_genomes, g.Ls, g.wps, g.Lw, g.stripes,
-            d_ws.as<uint32_t>());
-    }
-    PGX_HIP(hipGetLastError());
-    {
-        const size_t want = ((size_t)n_iter * n_genomes + 255) / 256;
-        ProfScope prof(ctx, "pan_core_reduce_kernel", ctx->stream);
-        pan_core_reduce_table_kernel<<<(uint32_t)(want < 2048 ? want : 2048), 256, 0, ctx->stream>>>(
-            d_ws.as<uint32_t>(), g.partials, n_iter, n_genomes, d_table.as<double>());
-    }
-    PGX_HIP(hipGetLastError());
-    PGX_HIP(hipMemcpyAsync(out_table, d_table.p, nperm * 4, hipMemcpyDeviceToHost, ctx->stream));
+    rc = table_from_device_bitmap(ctx, d_bits.as<uint64_t>(), n_genes, n_genomes, out_perms, n_iter, out_table);
+    if (rc != PGX_OK) return rc;
     PGX_HIP(hipStreamSynchronize(ctx->stream));
     return PGX_OK;
-}
+} catch (...) { return guarded_catch(__func__); }
 
 int pgx_row_counts_dev(pgx_ctx *ctx, const uint64_t *d_bits, uint32_t n_rows, uint32_t n_genomes, int32_t *d_counts,
-                       void *stream_) {
+                       void *stream_) try {
     PGX_REQUIRE(ctx, "NULL context");
     if (n_rows == 0) return PGX_OK;
     PGX_REQUIRE(d_bits && d_counts, "NULL argument");
@@ -689,27 +654,23 @@ int pgx_row_counts_dev(pgx_ctx *ctx, const uint64_t *d_bits, uint32_t n_rows, ui
     }
     PGX_HIP(hipGetLastError());
     return PGX_OK;
-}
+} catch (...) { return guarded_catch(__func__); }
 
 int pgx_row_counts(pgx_ctx *ctx, const int32_t *rows, const int32_t *genomes, uint64_t n_records, uint32_t n_rows,
-                   uint32_t n_genomes, int32_t *out_counts, uint64_t *out_duplicates) {
+                   uint32_t n_genomes, int32_t *out_counts, uint64_t *out_duplicates) try {
     PGX_REQUIRE(ctx, "NULL context");
     PGX_REQUIRE(n_records == 0 || (rows && genomes), "NULL record arrays");
     PGX_REQUIRE(n_rows == 0 || out_counts, "NULL argument");
     PGX_HIP(hipSetDevice(ctx->device_id));
     PcBuf d_bits(ctx, PC_SLOT_BITS), d_cnt(ctx, PC_SLOT_CNT), d_counts(ctx, PC_SLOT_COUNTS);
-    int rc = upload_and_build_bitmap(ctx, rows, genomes, n_records, n_rows, n_genomes, d_bits, d_cnt);
+    int rc = pgx_upload_and_build_bitmap(ctx, rows, genomes, n_records, n_rows, n_genomes, PC_SLOT_ROWS, PC_SLOT_GENOMES,
+                                         d_bits, d_cnt);
     if (rc != PGX_OK) return rc;
     PGX_HIP(d_counts.alloc((size_t)n_rows * 4));
     rc = pgx_row_counts_dev(ctx, d_bits.as<uint64_t>(), n_rows, n_genomes, d_counts.as<int32_t>(), ctx->stream);
     if (rc != PGX_OK) return rc;
-    uint64_t cnt[2] = {0, 0};
     if (n_rows) PGX_HIP(hipMemcpyAsync(out_counts, d_counts.p, (size_t)n_rows * 4, hipMemcpyDeviceToHost, ctx->stream));
-    PGX_HIP(hipMemcpyAsync(cnt, d_cnt.p, 16, hipMemcpyDeviceToHost, ctx->stream));
-    PGX_HIP(hipStreamSynchronize(ctx->stream));
-    PGX_REQUIRE(cnt[1] == 0, "record with row or genome index out of range");
-    if (out_duplicates) *out_duplicates = cnt[0];
-    return PGX_OK;
-}
+    return pgx_read_record_counters(ctx, d_cnt, out_duplicates);
+} catch (...) { return guarded_catch(__func__); }
 
 }  // extern "C"

@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstring>
 #include "../../include/pgx.h"
+#include "pgx_guard.h"
 
 #include <string>
 #include <utility>
@@ -100,8 +101,6 @@ struct ProfScope {
     ~ProfScope();
 };
 
-void pgx_set_error(const char *fmt, ...);
-
 #define PGX_HIP(call)                                                                      \
     do {                                                                                   \
         hipError_t e_ = (call);                                                            \
@@ -165,6 +164,16 @@ static inline uint32_t ceil_div_u32(uint32_t a, uint32_t b) { return (a + b - 1)
 // take the plain call. Returns when every chunk has been ENQUEUED (the source may be reused; the copies complete in
 // stream order).
 int pgx_staged_h2d(pgx_ctx *ctx, void *dst, const void *src, size_t bytes, hipStream_t stream);
+
+// COO records (host) -> gene x genome bitmap in d_bits, built on ctx->stream (pancore.hip). The coordinates travel
+// through the workspace slots slot_rows / slot_genomes; d_bits and d_cnt are the caller's (bound to slots of its own,
+// so that one user's table is not overwritten by another's call). d_cnt: 2 x u64, see presence_bitmap_kernel.
+int pgx_upload_and_build_bitmap(pgx_ctx *ctx, const int32_t *rows, const int32_t *genomes, uint64_t n_records,
+                                uint32_t n_rows, uint32_t n_genomes, int slot_rows, int slot_genomes, DevBuf &d_bits,
+                                DevBuf &d_cnt);
+// Its counterpart: the two counters back, ctx->stream synchronised; fails when a record was out of range (none of
+// those was written), stores the number of duplicate coordinates through out_duplicates unless that is NULL.
+int pgx_read_record_counters(pgx_ctx *ctx, DevBuf &d_cnt, uint64_t *out_duplicates);
 
 // all-gather of `count` uint64 per process with the context's RCCL communicator, enqueued on `stream` (rccl_exchange.hip)
 int pgx_rccl_all_gather_u64(pgx_ctx *ctx, const void *send, void *recv, size_t count, hipStream_t stream);

@@ -73,6 +73,17 @@ def test_evaluations_match_the_reference(path, gpu_ctx):
             assert_evaluation(out, z['point_ll'][k], z['point_grad'][k], z['point_scale'][k])
             again = gpu_ctx.bernoulli_eval(pt, exact=exact)
             assert out.tobytes() == again.tobytes()                  # bit-identical from call to call
+    # pan/core calls on the same context build ANOTHER table (another shape) through the same upload helper, in slots
+    # of their own: the loaded table is still the one that is evaluated
+    before = gpu_ctx.bernoulli_eval(z['points'][0])
+    rng = np.random.default_rng(5)
+    G2, S2 = G + 70, S + 3
+    r2, c2 = (a.astype(np.int32) for a in np.nonzero(rng.random((G2, S2)) < 0.5))
+    perms = np.array([rng.permutation(S2) for _ in range(3)], dtype=np.int32)
+    pan, core, dup = gpu_ctx.pan_core_coo(r2, c2, G2, S2, perms)
+    counts, dup2 = gpu_ctx.row_counts(r2, c2, G2, S2)
+    assert dup == 0 and dup2 == 0 and pan[0, -1] == np.count_nonzero(counts) and int(counts.sum()) == r2.size
+    assert gpu_ctx.bernoulli_eval(z['points'][0]).tobytes() == before.tobytes()
 
 
 def test_pad_bits_are_not_cells(gpu_ctx):
