@@ -15,6 +15,8 @@
  *                                       numpy likelihood and gradient -> pgx_bernoulli_*
  *   pangenome_analysis.py:457-492       ks_montecarlo_bbn() / draw_bbn(): np.random.choice
  *                                       and the per-iteration eCDF loop -> pgx_bbn_*
+ *   fcd.py:15-138, :199-219             formal_concept_decomposition() / compute_concept_coverage(): the dense
+ *                                       np.ix_ block sums -> pgx_fcd*
  *
  * The reference-side binding is a ctypes stub. Conventions:
  *   - every function returns 0 on success and a negative pgx_status on error;
@@ -419,6 +421,60 @@ int pgx_bbn_ks_sim(pgx_ctx *ctx, const double *draw_cdf, const double *model_cdf
                    uint32_t iterations, uint32_t *mt_key, int32_t *mt_pos, uint64_t chunk_draws, double *out_ks_sim);
 int pgx_bbn_draws(pgx_ctx *ctx, const double *draw_cdf, uint32_t sim_limit, uint64_t size, uint32_t *mt_key,
                   int32_t *mt_pos, uint64_t chunk_draws, int64_t *out_idx);
+
+/* Formal concept decomposition (formal_concept_decomposition / compute_concept_coverage, reference fcd.py:15-138,
+ * :199-219): the binary table is covered greedily with all-ones blocks ("concepts": a set of rows x a set of genomes).
+ * U = the ones not covered yet (a working copy on the device; the table itself is never written). While ones are left
+ * and fewer than `limit` concepts exist: acc = the rows with a one in U, live = the columns with a one in U, then, as long
+ * as it raises the score, the live column with the largest score (the lowest index among equals) joins the concept and
+ * acc &= that column of U (of the table under PGX_FCD_OVERLAP). With k columns merged and cnt[c] = popcount(U[:, c] & acc):
+ *   default               score[c] = (k + 1) * cnt[c]                                        (int64)
+ *   PGX_FCD_DIM_BALANCE   score[c] = dim_factors[k] * (double)cnt[c]   (one float64 multiply; dim_factors: HOST array of
+ *                         n_genomes doubles, the caller's ((k + 1) ** (log(n_rows) / log(n_genomes))); ignored under overlap)
+ *   PGX_FCD_OVERLAP       score[c] = cnt[c] + sum over the rows r of table[:, c] & acc of w[r],  w[r] = the ones U has
+ *                         in row r among the merged columns                                   (int64)
+ * The concept is (rows of acc ascending, columns in the order they joined); its block is cleared in U.
+ * Two calls: one of pgx_fcd / pgx_fcd_resident / pgx_fcd_dev runs the decomposition and keeps the concepts in the
+ * context; out_info says how many there are; pgx_fcd_fetch copies them out -- out_rows [n_row_entries] and out_cols
+ * [n_col_entries] hold the concepts' rows / columns end to end, concept i owns [offsets[i], offsets[i + 1]) of each
+ * (n_concepts + 1 offsets), out_left[i] = the ones still uncovered after concept i -- until the next run on the context.
+ *   pgx_fcd            HOST COO coordinates of the table; out_duplicates as pgx_presence_bitmap (may be NULL): with
+ *                      duplicate coordinates nothing is decomposed (out_info all zero)
+ *   pgx_fcd_resident   the table is read from the bitmap a pipeline left resident (pgx_bitmap_from_clusters), which is not
+ *                      modified: row i / column j of the table = row row_map[i] / column col_map[j] of it (col_map NULL:
+ *                      column j). A stale token fails with PGX_ERR_INVALID.
+ *   pgx_fcd_dev        d_bits: the table in the bitmap layout above (DEVICE, 16-byte aligned, pad bits zero, not written),
+ *                      a caller workspace of pgx_fcd_workspace_bytes(). Unlike the other *_dev entry points it is not
+ *                      graph-capturable: every step reads 16 bytes back, so it synchronises `stream` (plain launches on
+ *                      that stream only; at most n_genomes steps per concept and `limit` concepts).
+ * A concept that clears nothing (the reference would loop for ever) fails with PGX_ERR_INTERNAL.
+ *   pgx_fcd_coverage   out_cleared[i] = the ones concept i clears when the given concepts (layout as pgx_fcd_fetch's; no
+ *                      column twice in one concept) are cleared from the table one after the other with the same kernel;
+ *                      out_ones = the ones of the table. */
+#define PGX_FCD_OVERLAP 1u
+#define PGX_FCD_DIM_BALANCE 2u
+typedef struct pgx_fcd_info_t {
+    uint64_t n_concepts;
+    uint64_t n_row_entries;    /* sum of the concepts' row counts */
+    uint64_t n_col_entries;    /* sum of the concepts' column counts */
+    uint64_t steps;            /* score evaluations (one masked popcount of every live column each) */
+    uint64_t ones_total;       /* ones of the table */
+    uint64_t ones_left;        /* of those, not covered (0 unless `limit` stopped the decomposition) */
+} pgx_fcd_info_t;
+size_t pgx_fcd_workspace_bytes(uint32_t n_rows, uint32_t n_genomes);
+int pgx_fcd(pgx_ctx *ctx, const int32_t *rows, const int32_t *genomes, uint64_t n_records, uint32_t n_rows,
+            uint32_t n_genomes, uint64_t limit, uint32_t flags, const double *dim_factors, pgx_fcd_info_t *out_info,
+            uint64_t *out_duplicates);
+int pgx_fcd_resident(pgx_ctx *ctx, uint64_t token, const int32_t *row_map, const int32_t *col_map, uint32_t n_rows,
+                     uint32_t n_genomes, uint64_t limit, uint32_t flags, const double *dim_factors, pgx_fcd_info_t *out_info);
+int pgx_fcd_dev(pgx_ctx *ctx, const uint64_t *d_bits, uint32_t n_rows, uint32_t n_genomes, uint64_t limit, uint32_t flags,
+                const double *dim_factors, void *d_workspace, size_t workspace_bytes, void *stream, pgx_fcd_info_t *out_info);
+int pgx_fcd_fetch(pgx_ctx *ctx, int32_t *out_rows, uint64_t *out_row_offsets, int32_t *out_cols, uint64_t *out_col_offsets,
+                  uint64_t *out_left);
+int pgx_fcd_coverage(pgx_ctx *ctx, const int32_t *rows, const int32_t *genomes, uint64_t n_records, uint32_t n_rows,
+                     uint32_t n_genomes, const int32_t *concept_rows, const uint64_t *row_offsets, const int32_t *concept_cols,
+                     const uint64_t *col_offsets, uint64_t n_concepts, uint64_t *out_cleared, uint64_t *out_ones,
+                     uint64_t *out_duplicates);
 
 /* feature names (pangenome.py:1944-1969) as fixed-width zero-padded ASCII records (numpy 'S<width>'):
  * <prefix><cluster>[<variant><member>]; variant NULL = gene names */

@@ -62,6 +62,14 @@ class FastaInfo(C.Structure):
                 ('reserved', C.c_uint32), ('why', C.c_char * 256)]
 
 
+class FcdInfo(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ('n_concepts', 'n_row_entries', 'n_col_entries', 'steps', 'ones_total',
+                                          'ones_left')]
+
+
+FCD_OVERLAP, FCD_DIM_BALANCE = 1, 2    # PGX_FCD_OVERLAP, PGX_FCD_DIM_BALANCE
+
+
 # every symbol include/pgx.h declares: (restype, argtypes)
 _P = C.c_void_p
 _S = C.c_char_p
@@ -128,6 +136,16 @@ SIGNATURES = {
     'pgx_bbn_ks_sim': (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, C.POINTER(C.c_int32),
                                  C.c_uint64, _P]),
     'pgx_bbn_draws': (C.c_int, [_P, _P, C.c_uint32, C.c_uint64, _P, C.POINTER(C.c_int32), C.c_uint64, _P]),
+    'pgx_fcd_workspace_bytes': (C.c_size_t, [C.c_uint32, C.c_uint32]),
+    'pgx_fcd': (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, _P, C.POINTER(FcdInfo),
+                          C.POINTER(C.c_uint64)]),
+    'pgx_fcd_resident': (C.c_int, [_P, C.c_uint64, _P, _P, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, _P,
+                                   C.POINTER(FcdInfo)]),
+    'pgx_fcd_dev': (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, _P, _P, C.c_size_t, _P,
+                              C.POINTER(FcdInfo)]),
+    'pgx_fcd_fetch': (C.c_int, [_P, _P, _P, _P, _P, _P]),
+    'pgx_fcd_coverage': (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P, _P, _P, C.c_uint64, _P,
+                                   C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     'pgx_cluster_greedy': (C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(ClusterParams), _P, _P, _P, _P,
                                      C.POINTER(C.c_uint32), C.POINTER(ClusterStats)]),
     'pgx_cluster_window_cap': (C.c_uint32, [C.POINTER(ClusterParams)]),
@@ -483,6 +501,85 @@ class Context(object):
         check(lib().pgx_bbn_draws(self._h, _ptr(draw_cdf), draw_cdf.size, int(size), _ptr(key), C.byref(p),
                                   int(chunk_draws), _ptr(out)))
         return out, int(p.value)
+
+    # -- formal concept decomposition (fcd.formal_concept_decomposition / compute_concept_coverage) --------------------
+    @staticmethod
+    def _fcd_args(n_genomes, limit, overlap, dim_factors):
+        flags = FCD_OVERLAP if overlap else 0
+        if dim_factors is not None:
+            dim_factors = np.ascontiguousarray(dim_factors, dtype=np.float64)
+            if dim_factors.shape != (int(n_genomes),):
+                raise ValueError('dim_factors must hold one factor per genome')
+            flags |= FCD_DIM_BALANCE
+        if not 0 <= int(limit) < 2 ** 64:
+            raise ValueError('limit out of range')
+        return flags, dim_factors
+
+    def _fcd_fetch(self, info):
+        """The concepts of the run that has just ended: {'rows', 'row_offsets', 'cols', 'col_offsets' (a concept's rows
+        ascending / its columns in the order they joined, end to end, and n + 1 offsets), 'left' (ones uncovered after
+        each concept), 'steps', 'ones_total', 'ones_left'}."""
+        n = int(info.n_concepts)
+        out = {'rows': np.empty(int(info.n_row_entries), dtype=np.int32), 'row_offsets': np.empty(n + 1, dtype=np.uint64),
+               'cols': np.empty(int(info.n_col_entries), dtype=np.int32), 'col_offsets': np.empty(n + 1, dtype=np.uint64),
+               'left': np.empty(n, dtype=np.uint64)}
+        check(lib().pgx_fcd_fetch(self._h, _ptr(out['rows']), _ptr(out['row_offsets']), _ptr(out['cols']),
+                                  _ptr(out['col_offsets']), _ptr(out['left'])))
+        out.update(steps=int(info.steps), ones_total=int(info.ones_total), ones_left=int(info.ones_left))
+        return out
+
+    def fcd(self, rows, genomes, n_rows, n_genomes, limit, overlap=False, dim_factors=None):
+        """(concepts, duplicates) of the binary table with the given COO coordinates (pgx.h: pgx_fcd + pgx_fcd_fetch);
+        with duplicate coordinates nothing is decomposed and concepts is None."""
+        rows, genomes = _coo_args(rows, genomes)
+        flags, dim_factors = self._fcd_args(n_genomes, limit, overlap, dim_factors)
+        info, dup = FcdInfo(), C.c_uint64(0)
+        check(lib().pgx_fcd(self._h, _ptr(rows), _ptr(genomes), rows.size, int(n_rows), int(n_genomes), int(limit), flags,
+                            _ptr(dim_factors), C.byref(info), C.byref(dup)))
+        if dup.value:
+            return None, int(dup.value)
+        return self._fcd_fetch(info), 0
+
+    def fcd_resident(self, token, row_map, col_map, n_genomes, limit, overlap=False, dim_factors=None):
+        """The same from the bitmap a pipeline left resident under `token` (not modified): row i / column j of the table is
+        row row_map[i] / column col_map[j] (None: j) of it. Raises PgxError when the token is stale."""
+        row_map = np.ascontiguousarray(row_map, dtype=np.int32)
+        if col_map is not None:
+            col_map = np.ascontiguousarray(col_map, dtype=np.int32)
+            if col_map.shape != (int(n_genomes),):
+                raise ValueError('col_map must hold one entry per genome')
+        flags, dim_factors = self._fcd_args(n_genomes, limit, overlap, dim_factors)
+        info = FcdInfo()
+        check(lib().pgx_fcd_resident(self._h, int(token), _ptr(row_map), _ptr(col_map), row_map.size, int(n_genomes),
+                                     int(limit), flags, _ptr(dim_factors), C.byref(info)))
+        return self._fcd_fetch(info)
+
+    def fcd_dev(self, d_bits, n_rows, n_genomes, limit, d_ws, ws_bytes, overlap=False, dim_factors=None, stream=0):
+        """The same on a bitmap in device memory (raw device addresses; synchronises `stream`, see pgx.h)."""
+        flags, dim_factors = self._fcd_args(n_genomes, limit, overlap, dim_factors)
+        info = FcdInfo()
+        check(lib().pgx_fcd_dev(self._h, d_bits, int(n_rows), int(n_genomes), int(limit), flags, _ptr(dim_factors), d_ws,
+                                int(ws_bytes), stream, C.byref(info)))
+        return self._fcd_fetch(info)
+
+    def fcd_coverage(self, rows, genomes, n_rows, n_genomes, concept_rows, row_offsets, concept_cols, col_offsets):
+        """(cleared uint64[n_concepts], ones, duplicates): the ones each concept clears when they are cleared from the
+        table one after the other, and the ones of the table (pgx.h: pgx_fcd_coverage)."""
+        rows, genomes = _coo_args(rows, genomes)
+        concept_rows = np.ascontiguousarray(concept_rows, dtype=np.int32)
+        concept_cols = np.ascontiguousarray(concept_cols, dtype=np.int32)
+        row_offsets = np.ascontiguousarray(row_offsets, dtype=np.uint64)
+        col_offsets = np.ascontiguousarray(col_offsets, dtype=np.uint64)
+        n = row_offsets.size - 1
+        if n < 0 or col_offsets.size != n + 1 or (n and (int(row_offsets[n]) != concept_rows.size
+                                                         or int(col_offsets[n]) != concept_cols.size)):
+            raise ValueError('offsets do not match the concept arrays')
+        cleared = np.zeros(max(n, 0), dtype=np.uint64)
+        ones, dup = C.c_uint64(0), C.c_uint64(0)
+        check(lib().pgx_fcd_coverage(self._h, _ptr(rows), _ptr(genomes), rows.size, int(n_rows), int(n_genomes),
+                                     _ptr(concept_rows), _ptr(row_offsets), _ptr(concept_cols), _ptr(col_offsets), n,
+                                     _ptr(cleared), C.byref(ones), C.byref(dup)))
+        return cleared, int(ones.value), int(dup.value)
 
     def pan_core(self, bits, n_genes, perms):
         perms = np.ascontiguousarray(perms, dtype=np.int32)

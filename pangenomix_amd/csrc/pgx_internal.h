@@ -47,6 +47,10 @@ struct pgx_ctx {
     // the table loaded for Bernoulli likelihood evaluations (pgx_bernoulli_load*): its shape; the bitmap is a workspace slot
     uint32_t bern_genes = 0, bern_genomes = 0;
     bool bern_loaded = false;
+    // the concepts of the last formal concept decomposition (pgx_fcd*), kept for pgx_fcd_fetch: row / column indices of
+    // all concepts end to end, the offsets of each concept in them (n + 1 entries), the ones left uncovered after each
+    std::vector<int32_t> fcd_rows, fcd_cols;
+    std::vector<uint64_t> fcd_row_off, fcd_col_off, fcd_left;
     // the library's own RCCL communicator (pgx_rccl_comm_create): the record-sharded exchange without a callback
     void *comm = nullptr;
     int comm_rank = 0, comm_world = 0;
@@ -152,7 +156,7 @@ struct DevBuf {
 };
 
 // Workspace slot of the pipeline's resident bitmap (pancore.hip), read in place by bernoulli.hip. Slots in use:
-// pancore 80-94, heaps 96-98, bernoulli 100-107, betabinom 110-116 (host staging slots 110-112).
+// pancore 80-94, heaps 96-98, bernoulli 100-107, betabinom 110-116 (host staging slots 110-112), fcd 120-129 (host scratch slot 120).
 constexpr int PGX_SLOT_RESIDENT = 90;
 
 static inline uint32_t ceil_div_u32(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
