@@ -17,6 +17,8 @@
  *                                       and the per-iteration eCDF loop -> pgx_bbn_*
  *   fcd.py:15-138, :199-219             formal_concept_decomposition() / compute_concept_coverage(): the dense
  *                                       np.ix_ block sums -> pgx_fcd*
+ *   sparse_utils.py:73-109, ml_pipelines.py:349-388   compress_rows_spmatrix() / contingency_tables_from_sparse(): the
+ *                                       per-phenotype association screen -> pgx_assoc*
  *
  * The reference-side binding is a ctypes stub. Conventions:
  *   - every function returns 0 on success and a negative pgx_status on error;
@@ -475,6 +477,41 @@ int pgx_fcd_coverage(pgx_ctx *ctx, const int32_t *rows, const int32_t *genomes, 
                      uint32_t n_genomes, const int32_t *concept_rows, const uint64_t *row_offsets, const int32_t *concept_cols,
                      const uint64_t *col_offsets, uint64_t n_concepts, uint64_t *out_cleared, uint64_t *out_ones,
                      uint64_t *out_duplicates);
+
+/* The association screen (reference sparse_utils.py:73-109 compress_rows_spmatrix, ml_pipelines.py:349-388
+ * contingency_tables_from_sparse, :233-284 prepare_amr_case_data) on the table restricted to n_selected genomes
+ * (col_map[j] = the genome that is column j of the selection; NULL = all of them in order, n_selected = n_genomes):
+ *   incidence[r]      genomes of the selection row r is present in
+ *   tp[t][r]          of those, the genomes whose bit is set in mask t: masks holds n_targets x ceil(n_selected / 64)
+ *                     (at least 1) words, bit j % 64 of word j / 64 = column j of the selection; pad bits are ignored
+ *   PGX_ASSOC_BLOCKS  rows present in the same genomes of the selection form a block; blocks are numbered by their first
+ *                     row ascending: block_of_row[r] (n_rows entries), rep_row[b] = the first row of block b (room for
+ *                     n_rows entries, *out_n_blocks used). All rows without a genome form one block, unless
+ *   PGX_ASSOC_DROP_EMPTY  those rows take no part (block_of_row = -1): the blocks of the table without its empty rows.
+ * The result does not depend on the order in which the device's waves run. The bitmap is never written.
+ *   pgx_assoc            HOST COO coordinates of the table; out_duplicates as pgx_presence_bitmap (may be NULL): with
+ *                        duplicate coordinates nothing is computed
+ *   pgx_assoc_resident   the table is read from the bitmap a pipeline left resident (pgx_bitmap_from_clusters): row i of
+ *                        the table = row row_map[i] of it. A stale token fails with PGX_ERR_INVALID.
+ *   pgx_assoc_dev        d_bits: the table in the bitmap layout above; d_col_map, d_masks and the four result arrays are
+ *                        DEVICE pointers, the workspace is the caller's (pgx_assoc_workspace_bytes(), 16-byte aligned).
+ *                        Plain launches on `stream`, which is synchronised once at the end (status and block count back).
+ * out_tp / masks may be NULL with n_targets = 0; the block arrays may be NULL without PGX_ASSOC_BLOCKS. n_rows < 2^30. */
+#define PGX_ASSOC_BLOCKS 1u
+#define PGX_ASSOC_DROP_EMPTY 2u
+size_t pgx_assoc_workspace_bytes(uint32_t n_rows, uint32_t n_selected);
+int pgx_assoc(pgx_ctx *ctx, const int32_t *rows, const int32_t *genomes, uint64_t n_records, uint32_t n_rows,
+              uint32_t n_genomes, const int32_t *col_map, uint32_t n_selected, const uint64_t *masks, uint32_t n_targets,
+              uint32_t flags, uint32_t *out_tp, uint32_t *out_incidence, int32_t *out_block_of_row, int32_t *out_rep_row,
+              uint32_t *out_n_blocks, uint64_t *out_duplicates);
+int pgx_assoc_resident(pgx_ctx *ctx, uint64_t token, const int32_t *row_map, uint32_t n_rows, uint32_t n_genomes,
+                       const int32_t *col_map, uint32_t n_selected, const uint64_t *masks, uint32_t n_targets, uint32_t flags,
+                       uint32_t *out_tp, uint32_t *out_incidence, int32_t *out_block_of_row, int32_t *out_rep_row,
+                       uint32_t *out_n_blocks);
+int pgx_assoc_dev(pgx_ctx *ctx, const uint64_t *d_bits, uint32_t n_rows, uint32_t n_genomes, const int32_t *d_col_map,
+                  uint32_t n_selected, const uint64_t *d_masks, uint32_t n_targets, uint32_t flags, uint32_t *d_tp,
+                  uint32_t *d_incidence, int32_t *d_block_of_row, int32_t *d_rep_row, void *d_workspace,
+                  size_t workspace_bytes, void *stream, uint32_t *out_n_blocks);
 
 /* feature names (pangenome.py:1944-1969) as fixed-width zero-padded ASCII records (numpy 'S<width>'):
  * <prefix><cluster>[<variant><member>]; variant NULL = gene names */

@@ -68,6 +68,7 @@ class FcdInfo(C.Structure):
 
 
 FCD_OVERLAP, FCD_DIM_BALANCE = 1, 2    # PGX_FCD_OVERLAP, PGX_FCD_DIM_BALANCE
+ASSOC_BLOCKS, ASSOC_DROP_EMPTY = 1, 2  # PGX_ASSOC_BLOCKS, PGX_ASSOC_DROP_EMPTY
 
 
 # every symbol include/pgx.h declares: (restype, argtypes)
@@ -146,6 +147,13 @@ SIGNATURES = {
     'pgx_fcd_fetch': (C.c_int, [_P, _P, _P, _P, _P, _P]),
     'pgx_fcd_coverage': (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P, _P, _P, C.c_uint64, _P,
                                    C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    'pgx_assoc_workspace_bytes': (C.c_size_t, [C.c_uint32, C.c_uint32]),
+    'pgx_assoc': (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32, _P, _P,
+                            _P, _P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    'pgx_assoc_resident': (C.c_int, [_P, C.c_uint64, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32,
+                                     _P, _P, _P, _P, C.POINTER(C.c_uint32)]),
+    'pgx_assoc_dev': (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P,
+                                C.c_size_t, _P, C.POINTER(C.c_uint32)]),
     'pgx_cluster_greedy': (C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(ClusterParams), _P, _P, _P, _P,
                                      C.POINTER(C.c_uint32), C.POINTER(ClusterStats)]),
     'pgx_cluster_window_cap': (C.c_uint32, [C.POINTER(ClusterParams)]),
@@ -580,6 +588,71 @@ class Context(object):
                                      _ptr(concept_rows), _ptr(row_offsets), _ptr(concept_cols), _ptr(col_offsets), n,
                                      _ptr(cleared), C.byref(ones), C.byref(dup)))
         return cleared, int(ones.value), int(dup.value)
+
+    # -- association screen (sparse_utils.compress_rows*, ml_pipelines.contingency_tables_from_sparse) -------------------
+    @staticmethod
+    def _assoc_args(n_rows, n_genomes, col_map, masks, blocks, drop_empty):
+        n_rows, n_genomes = int(n_rows), int(n_genomes)
+        if col_map is not None:
+            col_map = np.ascontiguousarray(col_map, dtype=np.int32)
+            if col_map.ndim != 1:
+                raise ValueError('col_map must be 1-D')
+        n_sel = n_genomes if col_map is None else int(col_map.size)
+        words = max(1, (n_sel + 63) // 64)
+        n_targets = 0
+        if masks is not None:
+            masks = np.ascontiguousarray(masks, dtype=np.uint64)
+            if masks.ndim != 2 or masks.shape[1] != words:
+                raise ValueError('masks must be [n_targets, %d] words' % words)
+            n_targets = int(masks.shape[0])
+        flags = (ASSOC_BLOCKS if blocks else 0) | (ASSOC_DROP_EMPTY if blocks and drop_empty else 0)
+        out = {'tp': np.zeros((n_targets, n_rows), dtype=np.uint32), 'incidence': np.zeros(n_rows, dtype=np.uint32),
+               'block_of_row': np.full(n_rows if blocks else 0, -1, dtype=np.int32),
+               'rep_row': np.zeros(n_rows if blocks else 0, dtype=np.int32)}
+        return col_map, n_sel, masks, n_targets, flags, out
+
+    @staticmethod
+    def _assoc_out(out, blocks, n_blocks):
+        out['rep_row'] = out['rep_row'][:int(n_blocks.value)] if blocks else None
+        if not blocks:
+            out['block_of_row'] = None
+        return out
+
+    def assoc(self, rows, genomes, n_rows, n_genomes, col_map=None, masks=None, blocks=False, drop_empty=False):
+        """({'tp' uint32 [n_targets, n_rows], 'incidence' uint32 [n_rows], 'block_of_row' int32 [n_rows], 'rep_row' int32
+        [n_blocks]}, duplicates) of the binary table with the given COO coordinates, restricted to the genomes col_map
+        (pgx.h: pgx_assoc); with duplicate coordinates nothing is computed and the dict is None."""
+        rows, genomes = _coo_args(rows, genomes)
+        col_map, n_sel, masks, n_targets, flags, out = self._assoc_args(n_rows, n_genomes, col_map, masks, blocks, drop_empty)
+        n_blocks, dup = C.c_uint32(0), C.c_uint64(0)
+        check(lib().pgx_assoc(self._h, _ptr(rows), _ptr(genomes), rows.size, int(n_rows), int(n_genomes), _ptr(col_map), n_sel,
+                              _ptr(masks), n_targets, flags, _ptr(out['tp']), _ptr(out['incidence']),
+                              _ptr(out['block_of_row']), _ptr(out['rep_row']), C.byref(n_blocks), C.byref(dup)))
+        if dup.value:
+            return None, int(dup.value)
+        return self._assoc_out(out, blocks, n_blocks), 0
+
+    def assoc_resident(self, token, row_map, n_genomes, col_map=None, masks=None, blocks=False, drop_empty=False):
+        """The same from the bitmap a pipeline left resident under `token` (not modified): row i of the table is row
+        row_map[i] of it. Raises PgxError when the token is stale."""
+        row_map = np.ascontiguousarray(row_map, dtype=np.int32)
+        col_map, n_sel, masks, n_targets, flags, out = self._assoc_args(row_map.size, n_genomes, col_map, masks, blocks,
+                                                                        drop_empty)
+        n_blocks = C.c_uint32(0)
+        check(lib().pgx_assoc_resident(self._h, int(token), _ptr(row_map), row_map.size, int(n_genomes), _ptr(col_map), n_sel,
+                                       _ptr(masks), n_targets, flags, _ptr(out['tp']), _ptr(out['incidence']),
+                                       _ptr(out['block_of_row']), _ptr(out['rep_row']), C.byref(n_blocks)))
+        return self._assoc_out(out, blocks, n_blocks)
+
+    def assoc_dev(self, d_bits, n_rows, n_genomes, d_col_map, n_selected, d_masks, n_targets, d_tp, d_incidence,
+                  d_block_of_row, d_rep_row, d_ws, ws_bytes, blocks=True, drop_empty=False, stream=0):
+        """The same on device memory (raw device addresses; synchronises `stream`, see pgx.h); returns n_blocks."""
+        flags = (ASSOC_BLOCKS if blocks else 0) | (ASSOC_DROP_EMPTY if blocks and drop_empty else 0)
+        n_blocks = C.c_uint32(0)
+        check(lib().pgx_assoc_dev(self._h, d_bits, int(n_rows), int(n_genomes), d_col_map, int(n_selected), d_masks,
+                                  int(n_targets), flags, d_tp, d_incidence, d_block_of_row, d_rep_row, d_ws, int(ws_bytes),
+                                  stream, C.byref(n_blocks)))
+        return int(n_blocks.value)
 
     def pan_core(self, bits, n_genes, perms):
         perms = np.ascontiguousarray(perms, dtype=np.int32)

@@ -5,7 +5,9 @@ format, the output contract of the pangenome hot path.
 Mirrors the reference interface of pangenomix/sparse_utils.py
 (`LightSparseDataFrame` :182-364, `read_lsdf` :18-42) for the members that sit
 on the hot path: constructor, `.index/.columns/.data/.shape`,
-`to_npz`, `read_lsdf`, plus the small dense helpers downstream consumers use.
+`to_npz`, `read_lsdf`, plus the small dense helpers downstream consumers use, and
+`compress_rows` / `compress_rows_spmatrix` (:45-109), whose row comparison runs on
+the device (csrc/assoc.hip).
 
 On-disk contract (pinned by tests/golden/cds/expected/*.npz):
   <f>.npz            scipy.sparse.save_npz of the COO matrix
@@ -102,6 +104,122 @@ def read_lsdf(npz_file, label_file=None):
         labels = [line.strip() for line in f]
     n_rows = data.shape[0]
     return LightSparseDataFrame(labels[:n_rows], labels[n_rows:], data)
+
+
+def _screen_table(S, who):
+    """(rows, cols, shape, resident) of the stored entries of a table handed to the association screen (compress_rows*,
+    ml_pipelines): a dense 2-D array of 0/1 values, a scipy.sparse matrix or a LightSparseDataFrame, read through its
+    coordinates and never densified. The device works on presence bits, which restates the reference only for a table
+    whose stored values are all 1: a stored zero (an entry to the reference's compress_rows, nothing to its sums) or any
+    other value raises ValueError rather than being interpreted; duplicate coordinates are found on the device while
+    the bitmap is built. `resident`: the pipeline's hand-off record of a table returned by build_cds_pangenome(), or None."""
+    resident = None
+    if isinstance(S, LightSparseDataFrame):
+        resident = getattr(S, '_pgx_resident', None)
+        if resident is not None and not (resident['shape'] == tuple(S.shape) and resident['data'] is S.data
+                                         and resident['nnz'] == int(S.data.nnz) and 'row_cluster' in resident):
+            resident = None                  # (no longer the table the pipeline returned)
+        S = S.data
+    not_binary = who + ' needs a binary (0/1) table without stored zeros'
+    if scipy.sparse.issparse(S):
+        coo = S if S.format == 'coo' else S.tocoo()
+        try:
+            ok = np.all(np.asarray(coo.data) == 1)
+        except TypeError:
+            raise ValueError(not_binary)
+        if not ok:
+            raise ValueError(not_binary)
+        return (np.asarray(coo.row, dtype=np.int32), np.asarray(coo.col, dtype=np.int32),
+                tuple(int(x) for x in coo.shape), resident)
+    X = np.asarray(S)
+    if X.ndim != 2:
+        raise ValueError(who + ' takes a 2-D table')
+    try:
+        ones = np.asarray(X == 1, dtype=bool)
+        ok = np.all(ones | np.asarray(X == 0, dtype=bool))
+    except TypeError:
+        raise ValueError(not_binary)
+    if not ok:
+        raise ValueError(not_binary)
+    rows, cols = np.nonzero(ones)
+    return rows.astype(np.int32), cols.astype(np.int32), X.shape, None
+
+
+def _screen(table, who, ctx=None, col_map=None, masks=None, blocks=False, drop_empty=False):
+    """The device pass of the association screen (csrc/assoc.hip) over a table of _screen_table():
+    {'incidence' uint32 [n_rows], 'tp' uint32 [n_targets, n_rows], 'block_of_row' int32 [n_rows], 'rep_row' int32
+    [n_blocks]} of the table restricted to the columns col_map (None: all). A table the pipeline left on the device is
+    read there; otherwise its coordinates go up. There is no CPU fallback."""
+    from . import _native
+    rows, cols, (n_rows, n_cols), resident = table
+    if n_rows == 0 or n_cols == 0:           # nothing to upload: every row is empty
+        n_targets = 0 if masks is None else len(masks)
+        one_block = blocks and n_rows > 0 and not drop_empty
+        return {'incidence': np.zeros(n_rows, dtype=np.uint32), 'tp': np.zeros((n_targets, n_rows), dtype=np.uint32),
+                'block_of_row': np.full(n_rows, 0 if one_block else -1, dtype=np.int32) if blocks else None,
+                'rep_row': np.zeros(1 if one_block else 0, dtype=np.int32) if blocks else None}
+    ctx = ctx or _native.default_context()
+    if resident is not None and resident['ctx'] is ctx:
+        try:
+            return ctx.assoc_resident(resident['token'], resident['row_cluster'], n_cols, col_map, masks, blocks, drop_empty)
+        except _native.PgxError as e:
+            if getattr(e, 'status', 0) != -1:            # (PGX_ERR_INVALID: another pipeline has replaced it since --
+                raise                                    #  the coordinates go up instead)
+    out, dup = ctx.assoc(rows, cols, n_rows, n_cols, col_map, masks, blocks, drop_empty)
+    if dup:
+        raise ValueError(who + ' needs a table without duplicate entries')
+    return out
+
+
+def _block_members(block_of_row, n_blocks):
+    """(order, offsets): the rows of block b, ascending, are order[offsets[b]:offsets[b + 1]] (rows of block -1 -- dropped
+    ones -- are left out)."""
+    block_of_row = np.asarray(block_of_row, dtype=np.int64)
+    order = np.argsort(block_of_row, kind='stable')
+    dropped = int(np.count_nonzero(block_of_row < 0))
+    counts = np.bincount(block_of_row[block_of_row >= 0], minlength=int(n_blocks))
+    offsets = np.zeros(int(n_blocks) + 1, dtype=np.int64)
+    np.cumsum(counts, out=offsets[1:])
+    return order[dropped:], offsets
+
+
+def compress_rows_spmatrix(spmat, ctx=None):
+    """Merge the rows of a sparse binary matrix that have the same set of non-zero columns (reference
+    sparse_utils.py:73-109). Returns (spblock, block_definitions): blocks are numbered by their first row; spblock is the
+    CSR matrix of those first rows and block_definitions[i] lists the rows of block i, ascending (a list of lists of numpy
+    integers). All empty rows form one block. The rows are compared on the device (hash table over the rows' bit
+    signatures, csrc/assoc.hip); `spmat` may also be a dense 0/1 array or a LightSparseDataFrame."""
+    who = 'compress_rows_spmatrix'
+    table = _screen_table(spmat, who)
+    out = _screen(table, who, ctx, blocks=True)
+    if isinstance(spmat, LightSparseDataFrame):
+        spmat = spmat.data
+    spdata = spmat.tocsr() if scipy.sparse.issparse(spmat) else scipy.sparse.csr_matrix(np.asarray(spmat))
+    order, offsets = _block_members(out['block_of_row'], out['rep_row'].size)
+    flat = list(order)                                  # numpy integers, as the reference's row positions are
+    bounds = offsets.tolist()
+    block_definitions = [flat[a:b] for a, b in zip(bounds[:-1], bounds[1:])]
+    return spdata[out['rep_row'], :], block_definitions
+
+
+def compress_rows(lsdf, ctx=None):
+    """compress_rows_spmatrix for a LightSparseDataFrame (reference sparse_utils.py:45-70): (lsdf_block,
+    block_definitions) with the blocks labelled B0, B1, ... and block_definitions[i] the array of the row LABELS of block
+    i. The gene table returned by build_cds_pangenome() is read from the bitmap the pipeline left on the device."""
+    who = 'compress_rows'
+    out = _screen(_screen_table(lsdf, who), who, ctx, blocks=True)
+    return _block_frame(lsdf, out['block_of_row'], out['rep_row'])
+
+
+def _block_frame(lsdf, block_of_row, rep_row, csr=None):
+    """(lsdf_block, block_definitions) of compress_rows from the device's block numbers over the rows of `lsdf` (csr: its
+    matrix in CSR form, where the caller has it)."""
+    order, offsets = _block_members(block_of_row, rep_row.size)
+    index_labels = ['B' + str(x) for x in np.arange(rep_row.size)]
+    lsdf_block = LightSparseDataFrame(index=index_labels, columns=lsdf.columns, data=(lsdf.data.tocsr() if csr is None else csr)[rep_row, :])
+    labels = lsdf.index[order]
+    bounds = offsets.tolist()
+    return lsdf_block, [labels[a:b] for a, b in zip(bounds[:-1], bounds[1:])]
 
 
 class LightSparseDataFrame(object):
