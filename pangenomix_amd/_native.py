@@ -362,6 +362,17 @@ class Context(object):
         check(lib().pgx_pan_core_dev(self._h, d_bits, int(n_genes), int(n_genomes), d_perms, int(n_iter),
                                      d_pan, d_core, d_ws, int(ws_bytes), stream))
 
+    def row_counts_dev(self, d_bits, n_rows, n_genomes, d_counts, stream=0):
+        check(lib().pgx_row_counts_dev(self._h, d_bits, int(n_rows), int(n_genomes), d_counts, stream))
+
+    def heaps_fit_dev(self, d_pan, n_iter, n_genomes, d_alpha, d_kappa, stream=0):
+        """d_pan: int32 [n_iter, n_genomes], e.g. pan_core_dev's output in place."""
+        check(lib().pgx_heaps_fit_dev(self._h, d_pan, int(n_iter), int(n_genomes), d_alpha, d_kappa, stream))
+
+    def bernoulli_eval_dev(self, d_bits, n_genes, n_genomes, d_pq, d_out, d_ws, ws_bytes, flags=0, stream=0):
+        check(lib().pgx_bernoulli_eval_dev(self._h, d_bits, int(n_genes), int(n_genomes), d_pq, int(flags), d_out, d_ws,
+                                           int(ws_bytes), stream))
+
     # -- K3 ----------------------------------------------------------------
     def presence_bitmap(self, rows, genomes, n_rows, n_genomes, return_duplicates=False):
         rows, genomes = _coo_args(rows, genomes)

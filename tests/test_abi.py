@@ -56,3 +56,16 @@ def test_rccl_is_loaded_on_request_only_and_a_bad_path_is_an_error():
     needed = os.popen('readelf -d %s' % os.path.join(ROOT, 'pangenomix_amd', 'libpgx.so')).read()
     assert 'rccl' not in needed
     assert os.path.basename(_native.rccl_path()).startswith('librccl')
+
+
+def test_every_device_pointer_entry_has_a_wrapper_and_a_gpu_test():
+    """A pgx_*_dev entry cannot arrive untested: each has a Context method of the same stem, and that method's name
+    occurs in a tests/test_gpu_*.py file."""
+    import glob
+    entries = sorted(n for n in _native.SIGNATURES if n.endswith('_dev'))
+    assert len(entries) >= 9
+    text = ''.join(open(p).read() for p in sorted(glob.glob(os.path.join(ROOT, 'tests', 'test_gpu_*.py'))))
+    for name in entries:
+        method = name[len('pgx_'):]
+        assert callable(getattr(_native.Context, method, None)), '%s has no Context.%s' % (name, method)
+        assert re.search(r'\.%s\(' % method, text), 'no tests/test_gpu_*.py calls %s' % method

@@ -267,6 +267,26 @@ def test_device_pointer_entry_and_errors(gpu_ctx):
     d_bad = dev(bad)
     with pytest.raises(_native.PgxError, match='out of range'):
         gpu_ctx.assoc_dev(args[0], n_rows, n_cols, d_bad.data_ptr(), *args[4:], nws)
+    # the same with results and a workspace of exactly that size between guard bands and full of garbage, on a side
+    # stream whose earlier work makes the inputs (tests/dev_entry_checks.py)
+    import dev_entry_checks as chk
+    results = []
+    for fill in chk.FILLS:
+        with chk.stream_scope('side') as st:
+            ws, tp = chk.guarded(nws, fill), chk.guarded(3 * n_rows * 4, fill)
+            inc, block, rep = (chk.guarded(n_rows * 4, fill) for _ in range(3))
+            u_bits, u_map, u_masks = chk.upload(bits), chk.upload(col_map), chk.upload(masks)
+            with chk.unchanged(u_bits, u_map, u_masks):
+                nb = gpu_ctx.assoc_dev(u_bits.ptr, n_rows, n_cols, u_map.ptr, 170, u_masks.ptr, 3, tp.ptr, inc.ptr, block.ptr,
+                                       rep.ptr, ws.ptr, nws, blocks=True, drop_empty=True, stream=st)
+        for b in (ws, tp, inc, block, rep):
+            b.assert_guards_intact()
+        assert nb == want['rep_row'].size
+        results.append((tp.numpy(np.uint32).reshape(3, n_rows), inc.numpy(np.uint32), block.numpy(np.int32),
+                        rep.numpy(np.int32)[:nb]))
+    got = chk.same_bytes(results)
+    for g, k in zip(got, ('tp', 'incidence', 'block_of_row', 'rep_row')):
+        assert np.array_equal(g, want[k])
 
 
 def test_calls_in_a_row_reuse_the_workspace(gpu_ctx):

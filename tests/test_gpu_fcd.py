@@ -171,6 +171,19 @@ def test_device_pointer_entry(gpu_ctx):
     assert np.array_equal(d_bits.cpu().numpy().view(np.uint64), bits)
     with pytest.raises(_native.PgxError, match='workspace too small'):
         gpu_ctx.fcd_dev(d_bits.data_ptr(), n_rows, n_cols, 1, d_ws.data_ptr(), nws - 1)
+    # the same with a workspace of exactly that size between guard bands and full of garbage, on a side stream whose
+    # earlier work makes the bitmap (tests/dev_entry_checks.py)
+    import dev_entry_checks as chk
+    want = gpu_ctx.fcd(fx['rows'], fx['cols'], n_rows, n_cols, n_rows * n_cols)[0]
+    for fill in chk.FILLS:
+        with chk.stream_scope('side') as st:
+            ws = chk.guarded(nws, fill)
+            up = chk.upload(bits)
+            with chk.unchanged(up):
+                got = gpu_ctx.fcd_dev(up.ptr, n_rows, n_cols, n_rows * n_cols, ws.ptr, nws, stream=st)
+        ws.assert_guards_intact()
+        for k in ('rows', 'row_offsets', 'cols', 'col_offsets', 'left'):
+            assert np.array_equal(got[k], want[k])
 
 
 def test_verbose_prints_the_progress_line(capsys, gpu_ctx):
