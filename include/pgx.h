@@ -379,8 +379,12 @@ int pgx_pan_core_table_resident(pgx_ctx *ctx, uint64_t token, uint32_t n_genes, 
  * in fp64, with every cell's terms as these per-cell expressions give them (so nan / inf appear where they put them:
  * p_i q_j = 1 on a present cell gives nan in LL and in that row's and column's gradient). Deterministic: the same
  * inputs give the same bits on every call (no atomics; partials summed in an order fixed by the table's shape).
- * When every fl(p_i q_j) lies strictly inside (0, 1) the present cells' log terms are summed as
+ * When every fl(p_i q_j) is a normal number below 1 the present cells' log terms are summed as
  * rowsum_i log p_i + colsum_j log q_j; flags = PGX_BERNOULLI_EXACT evaluates every cell's own log instead.
+ * Accuracy: LL within 1e-12 x (the sum of its absolute terms) + 2^-52 x (present cells) of the per-cell sum, each
+ * gradient entry within 1e-12 x the sum of its absolute terms. The second LL term is log(fl(p q))'s own: up to 2^-53
+ * absolute per present cell, which the log p + log q form does not carry; it decides on tables with few absent cells
+ * near p q = 1, where |log(p q)| is about 1e-8 per cell.
  * pq = [P (n_genes); Q (n_genomes)], out = [LL; dL/dp (n_genes); dL/dq (n_genomes)].
  *   pgx_bernoulli_eval_dev      d_bits: the table in the bitmap layout above (pad bits zero; they are not cells);
  *                               DEVICE pointers and a caller workspace of pgx_bernoulli_workspace_bytes(); enqueues

@@ -12,7 +12,7 @@
 // with r = p q rounded once and 1 - r rounded once (no contraction into an fma), so that nan and inf appear where the
 // per-cell expressions put them (r = 1 on a present cell: 0 * log 0 = nan, 0 / 0 = nan).
 //
-// Fast mode: when every r lies strictly inside (0, 1) -- decided on the device from min / max of P and Q, see
+// Fast mode: when every r is a normal number below 1 -- decided on the device from min / max of P and Q, see
 // bern_mode_kernel -- a present cell contributes exactly 0 to both gradient sums and log(p q) to LL. Its LL term is
 // then taken as rowsum_i log p_i + colsum_j log q_j (one log per row and column instead of one per present cell) and
 // present cells cost nothing. Absent cells cost one log and one division per pass either way.
@@ -71,7 +71,7 @@ BernGeom make_geom(uint32_t G, uint32_t S) {
     return g;
 }
 
-// mode[0] = 0: fast mode (every fl(p_i q_j) in (0, 1)); 1: per-cell expressions everywhere. One block.
+// mode[0] = 0: fast mode (every fl(p_i q_j) normal and below 1); 1: per-cell expressions everywhere. One block.
 __global__ __launch_bounds__(1024) void bern_mode_kernel(const double *__restrict__ pq, uint32_t G, uint32_t S,
                                                          uint32_t force_exact, uint32_t *__restrict__ mode) {
     __shared__ double s_lo[2][1024], s_hi[2][1024];
@@ -102,8 +102,10 @@ __global__ __launch_bounds__(1024) void bern_mode_kernel(const double *__restric
     if (threadIdx.x == 0) {
 #pragma clang fp contract(off)
         const double pmin = s_lo[0][0], qmin = s_lo[1][0], pmax = s_hi[0][0], qmax = s_hi[1][0];
-        // rounding is monotonic: for positive operands fl(pmin qmin) <= fl(p q) <= fl(pmax qmax)
-        const bool inside = !s_bad[0] && pmin > 0.0 && qmin > 0.0 && pmin * qmin > 0.0 && pmax * qmax < 1.0;
+        // rounding is monotonic: for positive operands fl(pmin qmin) <= fl(p q) <= fl(pmax qmax). A subnormal
+        // fl(p q) has lost bits that log p + log q keeps (fl(1e-161 * 1e-161): 0.012 in its log), so the per-cell
+        // expressions take over below the smallest normal number, not only at 0.
+        const bool inside = !s_bad[0] && pmin > 0.0 && qmin > 0.0 && pmin * qmin >= 0x1p-1022 && pmax * qmax < 1.0;
         mode[0] = (force_exact || !inside) ? 1u : 0u;
     }
 }

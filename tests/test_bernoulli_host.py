@@ -1,6 +1,9 @@
 """compute_bernoulli_grid_core_genome without a GPU: LightSparseDataFrame.to_sparse_arrays() against the reference's
-frame (tests/golden/core/to_sparse_arrays.npz, written by tests/golden/make_golden_core.py), and the refusals that
-happen before any library call."""
+frame (tests/golden/core/to_sparse_arrays.npz, written by tests/golden/make_golden_core.py), the refusals that
+happen before any library call, and the yardstick of the GPU tests (tests/bernoulli_model.py): its geometry against the
+library's workspace size, its evaluate() against every fixture of the reference and against 50 digits."""
+import ctypes
+import glob
 import os
 
 import numpy as np
@@ -8,6 +11,7 @@ import pandas as pd
 import pytest
 import scipy.sparse
 
+import bernoulli_model as bm
 from pangenomix_amd import _native, sparse_utils
 from pangenomix_amd import pangenome_analysis as pa
 
@@ -94,3 +98,135 @@ def test_there_is_no_cpu_fallback():
         with pytest.raises(_native.PgxError) as err:
             pa.compute_bernoulli_grid_core_genome(frame, ctx=None)
         assert err.value.status == -2
+
+
+# ---- tests/bernoulli_model.py, the yardstick of test_gpu_bernoulli_geometry.py and test_gpu_bernoulli_edges.py ----------
+FIXTURES = sorted(p for d in ('core', 'bernoulli_edges') for p in glob.glob(os.path.join(HERE, 'golden', d, 'g*.npz')))
+
+
+def test_geometry_gives_the_librarys_workspace_size():
+    lib = ctypes.CDLL(os.path.join(os.path.dirname(HERE), 'pangenomix_amd', 'libpgx.so'))
+    lib.pgx_bernoulli_workspace_bytes.restype = ctypes.c_size_t
+    lib.pgx_bernoulli_workspace_bytes.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
+    rng = np.random.default_rng(2024)
+    shapes = bm.GEOMETRY_SHAPES + bm.EDGE_SHAPES + [(0, 0), (0, 7), (300, 0), (1, 1), (64, 16), (65, 17)]
+    for hi_g, hi_s in ((200, 200), (5000, 3000), (300000, 64), (64, 300000), (2000000, 1200)):
+        shapes += [(int(rng.integers(1, hi_g)), int(rng.integers(1, hi_s))) for _ in range(60)]
+    assert len(shapes) > 300
+    for G, S in shapes:
+        assert bm.geometry(G, S).workspace_bytes == lib.pgx_bernoulli_workspace_bytes(G, S), (G, S)
+
+
+def test_geometry_shapes_cover_every_class():
+    """The tables of test_gpu_bernoulli_geometry.py reach every path of the slab split: a ragged last slab of pass A (with
+    2 and with 3 slabs, and one of a single genome), two workgroups in x in pass A and in pass B, more than 1024 entries
+    of P and Q (the strided loops of the one-block mode and total kernels), more than one bitmap word per slab of pass B
+    with a ragged and with a full last slab, a last word with one valid bit, and a_slabs limited by the wave target."""
+    geo = {shape: bm.geometry(*shape) for shape in bm.GEOMETRY_SHAPES}
+    assert any(g.a_slabs == 2 and g.a_last < g.a_span for g in geo.values())
+    assert any(g.a_slabs == 3 and g.a_last < g.a_span for g in geo.values())
+    assert any(g.a_slabs > 1 and g.a_last == 1 for g in geo.values())
+    assert any(g.a_blocks == 2 and g.b_blocks == 2 for g in geo.values())
+    assert any(g.words == 1 and g.b_slabs == 1 and G + S > 1024 for (G, S), g in geo.items())
+    assert any(g.b_span == 2 and g.b_last == 1 and G % 64 == 1 for (G, S), g in geo.items())
+    assert any(g.b_span == 2 and g.b_last == 2 and G % 64 == 1 for (G, S), g in geo.items())
+    assert any(g.b_span == 2 and g.b_last == 2 and g.a_by_waves and g.a_last == g.a_span for g in geo.values())
+    assert any(not g.a_by_waves and g.a_slabs > 1 for g in geo.values())
+    # the table of the issue, field by field: a_slabs x a_span (last), b_slabs x b_span (last)
+    assert [tuple(geo[s][k] for k in (1, 2, 3, 6, 7, 8)) for s in bm.GEOMETRY_SHAPES] == [
+        (2, 9, 8, 5, 1, 1), (3, 14, 12, 5, 1, 1), (17, 16, 1, 5, 1, 1), (69, 16, 12, 1, 1, 1),
+        (17, 61, 49, 126, 2, 1), (5, 52, 49, 411, 2, 2), (4, 100, 100, 547, 2, 2)]
+    # what the fast tests over tests/golden/core reach, for the record: never more than one word per slab of pass B
+    assert all(bm.geometry(G, S).b_span == 1 for G, S in ((2000, 60), (65, 3), (3000, 70), (128, 12)))
+
+
+@pytest.mark.parametrize('path', FIXTURES, ids=[os.path.basename(p)[:-4] for p in FIXTURES])
+def test_evaluate_reproduces_the_references_fixtures(path):
+    """point_ll and point_grad of every fixture within the tolerances of test_gpu_bernoulli.assert_evaluation (the
+    fixtures of bernoulli_edges included: evaluate() takes log(fl(p q)) as the reference does), the specials in the same
+    places, and the recorded scales."""
+    z = np.load(path)
+    G, S = (int(v) for v in z['shape'])
+    for k, pt in enumerate(z['points']):
+        ev = bm.evaluate((z['rows'], z['cols'], (G, S)), pt)
+        bm.same_specials(ev.ll, z['point_ll'][k])
+        bm.same_specials(ev.grad, z['point_grad'][k])
+        if np.isfinite(z['point_ll'][k]):
+            np.testing.assert_allclose(ev.ll, z['point_ll'][k], rtol=1e-12, atol=0)
+        fin = np.isfinite(z['point_grad'][k])
+        assert np.all(np.abs(ev.grad - z['point_grad'][k])[fin] <= 1e-12 * z['point_scale'][k][fin])
+        np.testing.assert_allclose(ev.scale[fin], z['point_scale'][k][fin], rtol=1e-13)
+        if np.isfinite(z['point_ll_scale'][k]):
+            np.testing.assert_allclose(ev.ll_scale, z['point_ll_scale'][k], rtol=1e-13)
+        assert ev.present == z['rows'].size
+
+
+def literal_evaluation(X, pq):
+    """The per-cell expressions of pgx.h written out cell by cell, nothing skipped (longdouble)."""
+    G, S = X.shape
+    L = np.longdouble
+    with np.errstate(all='ignore'):
+        r = np.outer(pq[:G], pq[G:])
+        t = (1.0 - r).astype(L)
+        r, x, P, Q = r.astype(L), X.astype(L), pq[:G].astype(L)[:, None], pq[G:].astype(L)[None, :]
+        ll = (x * np.log(r) + (1 - x) * np.log(t)).sum()
+        dp = X.sum(1) / P[:, 0] - np.where(X, L(0) / t, Q / t).sum(1)
+        dq = X.sum(0) / Q[0] - np.where(X, L(0) / t, P / t).sum(0)
+    return np.float64(ll), np.concatenate((dp, dq)).astype(np.float64)
+
+
+SPECIAL_VALUES = [1.0, 2.0, 0.5, 0.0, -0.5, np.nan, np.inf, 1e-162, 1e-161]
+
+
+@pytest.mark.parametrize('value', SPECIAL_VALUES)
+@pytest.mark.parametrize('where', ['P', 'Q', 'both'])
+def test_evaluate_places_the_specials_as_the_per_cell_expressions_do(value, where):
+    """evaluate() takes each log and quotient only in the cells whose term it is and tells 0 * log and 0 / t from the
+    float64 operand; the literal expressions over every cell must put nan and inf in the same places and give the same
+    finite numbers."""
+    rng = np.random.default_rng(3)
+    G, S = 70, 5
+    X = rng.random((G, S)) < 0.5
+    X[11, 2], X[12, 2] = True, False
+    pq = rng.uniform(0.8, 0.99, G + S)
+    if where in ('P', 'both'):
+        pq[11] = pq[12] = value
+    if where in ('Q', 'both'):
+        pq[G + 2] = value
+    ev = bm.evaluate(X, pq)
+    ll, grad = literal_evaluation(X, pq)
+    bm.same_specials(ev.ll, ll)
+    bm.same_specials(ev.grad, grad)
+    if np.isfinite(ll):
+        np.testing.assert_allclose(ev.ll, ll, rtol=1e-15)
+    fin = np.isfinite(grad)
+    np.testing.assert_allclose(ev.grad[fin], grad[fin], rtol=1e-13, atol=0)
+    ev_coo = bm.evaluate(tuple(np.nonzero(X)) + ((G, S),), pq, threads=1)
+    assert all(np.array_equal(a, b, equal_nan=True) for a, b in zip(ev, ev_coo))
+
+
+@pytest.mark.parametrize('G,S', bm.EDGE_SHAPES)
+def test_evaluate_agrees_with_fifty_digits_on_the_edge_tables(G, S):
+    """The CPU proof that the yardstick alone stays inside the tolerances of the GPU tests. LL: ll_bound_exact. A
+    gradient entry: 1e-12 x its scale + 2 u x the sum over its absent cells of (r / t) |term|, because fl(p q) moves
+    t = 1 - r by u r / t relatively, and r / t reaches 5e7 at the upper bound (there the plain 1e-12 x scale cannot
+    hold against the TRUE p q: the worst entry is printed). Between evaluate() and the device, which round p q alike,
+    it is the plain 1e-12 x scale."""
+    worst_ll = worst_grad = worst_plain = 0.0
+    for name, X in bm.edge_tables(G, S).items():
+        for point, pq in bm.edge_points(X).items():
+            ev = bm.evaluate(X, pq)
+            ll, grad = bm.exact(X, pq)
+            bound = bm.ll_bound_exact(ev)
+            assert abs(ev.ll - ll) <= bound, (name, point, abs(ev.ll - ll), bound)
+            r = np.outer(pq[:G], pq[G:])
+            t = 1.0 - r
+            moved = np.where(X, 0.0, r / t / t)
+            slack = 2 * bm.U * np.concatenate(((moved * pq[None, G:]).sum(1), (moved * pq[:G, None]).sum(0)))
+            err = np.abs(ev.grad - grad)
+            assert np.all(err <= 1e-12 * ev.scale + slack), (name, point, float((err - slack).max()))
+            worst_ll = max(worst_ll, abs(ev.ll - ll) / bound)
+            worst_grad = max(worst_grad, float((err / (1e-12 * ev.scale + slack)).max()))
+            worst_plain = max(worst_plain, float((err / ev.scale).max()))
+    print('%d x %d: LL error / bound <= %.3g, gradient error / bound <= %.3g, gradient error / scale <= %.3g'
+          % (G, S, worst_ll, worst_grad, worst_plain))
