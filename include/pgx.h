@@ -19,6 +19,8 @@
  *                                       np.ix_ block sums -> pgx_fcd*
  *   sparse_utils.py:73-109, ml_pipelines.py:349-388   compress_rows_spmatrix() / contingency_tables_from_sparse(): the
  *                                       per-phenotype association screen -> pgx_assoc*
+ *   pangenome.py:1246-1330, :1812-1889  validate_gene_table[_dense]() / extract_dominant_alleles(): the Python loops
+ *                                       over allele rows or genome columns -> pgx_allele_runs*
  *
  * The reference-side binding is a ctypes stub. Conventions:
  *   - every function returns 0 on success and a negative pgx_status on error;
@@ -520,6 +522,42 @@ int pgx_assoc_dev(pgx_ctx *ctx, const uint64_t *d_bits, uint32_t n_rows, uint32_
                   uint32_t n_selected, const uint64_t *d_masks, uint32_t n_targets, uint32_t flags, uint32_t *d_tp,
                   uint32_t *d_incidence, int32_t *d_block_of_row, int32_t *d_rep_row, void *d_workspace,
                   size_t workspace_bytes, void *stream, uint32_t *out_n_blocks);
+
+/* Runs of allele rows (reference pangenome.py:1246-1330 validate_gene_table / validate_gene_table_dense, :1812-1889
+ * extract_dominant_alleles): run r is the allele rows [run_start[r], run_start[r + 1]) of the allele table -- run_start holds
+ * n_runs + 1 entries, starts at 0, never decreases and ends at or below n_alleles; a run may be empty, rows behind the last
+ * run belong to none. gene_of_run[r] is the row of the gene table run r is compared with, -1 = none (its gene bits are 0);
+ * gene_of_run NULL (or, for the device entry, no gene bitmap) = -1 everywhere. All three tables have n_genomes genomes.
+ *   derived          bitmap of n_runs rows in the layout above (n_genomes x pgx_bitmap_stride_words(n_runs) words): bit
+ *                    (r, j) is set iff genome j has a bit in any allele row of run r; pad bits are 0
+ *   diff             the same shape: derived XOR (bit gene_of_run[r] of the gene table, for every genome)
+ *   diff_per_genome  [n_genomes] set bits of the genome's words of diff;   diff_per_run [n_runs] set bits of row r of diff
+ *   total            [n_runs] uint64: the sum over the run's rows of the genomes that hold the row
+ *   best_allele      [n_runs] the first row of the run with the largest such count (a later row replaces an earlier one
+ *                    only with a strictly greater count), -1 for an empty run;   best_count [n_runs] that count (0 if empty)
+ * Every output pointer may be NULL; what is not asked for is not computed. The result does not depend on the order in which
+ * the device's waves run (no atomics on a result). Bits of the allele bitmap at or beyond n_alleles are masked, not trusted.
+ *   pgx_allele_runs      HOST COO coordinates of the allele table and (used only with gene_of_run) of the gene table;
+ *                        out_duplicates (2 x uint64: allele table, gene table; may be NULL) as pgx_presence_bitmap: with
+ *                        duplicate coordinates in either nothing is computed. run_start / gene_of_run that break the rules
+ *                        above, or n_runs = 0 with an output requested, fail with PGX_ERR_INVALID before anything is launched.
+ *   pgx_allele_runs_dev  d_allele_bits, d_gene_bits (may be NULL), d_run_start, d_gene_of_run (may be NULL), the result
+ *                        arrays and the workspace (pgx_allele_runs_workspace_bytes(), 16-byte aligned) are the caller's
+ *                        DEVICE pointers. Plain launches on `stream`, which is synchronised once at the end. The run arrays
+ *                        are checked on the device: the kernels clamp what they read (no access out of bounds), and arrays
+ *                        that break the rules fail with PGX_ERR_INVALID after the launches, the outputs then being unspecified.
+ * n_alleles, n_runs, n_genes, n_genomes < 2^31. */
+size_t pgx_allele_runs_workspace_bytes(uint32_t n_alleles, uint32_t n_runs, uint32_t n_genomes);
+int pgx_allele_runs(pgx_ctx *ctx, const int32_t *allele_rows, const int32_t *allele_genomes, uint64_t n_allele_records,
+                    uint32_t n_alleles, const int32_t *gene_rows, const int32_t *gene_genomes, uint64_t n_gene_records,
+                    uint32_t n_genes, uint32_t n_genomes, const uint32_t *run_start, uint32_t n_runs, const int32_t *gene_of_run,
+                    uint64_t *out_derived, uint64_t *out_diff, uint32_t *out_diff_per_genome, uint32_t *out_diff_per_run,
+                    uint64_t *out_total, int32_t *out_best_allele, uint32_t *out_best_count, uint64_t *out_duplicates);
+int pgx_allele_runs_dev(pgx_ctx *ctx, const uint64_t *d_allele_bits, uint32_t n_alleles, const uint64_t *d_gene_bits,
+                        uint32_t n_genes, uint32_t n_genomes, const uint32_t *d_run_start, uint32_t n_runs,
+                        const int32_t *d_gene_of_run, uint64_t *d_derived, uint64_t *d_diff, uint32_t *d_diff_per_genome,
+                        uint32_t *d_diff_per_run, uint64_t *d_total, int32_t *d_best_allele, uint32_t *d_best_count,
+                        void *d_workspace, size_t workspace_bytes, void *stream);
 
 /* feature names (pangenome.py:1944-1969) as fixed-width zero-padded ASCII records (numpy 'S<width>'):
  * <prefix><cluster>[<variant><member>]; variant NULL = gene names */

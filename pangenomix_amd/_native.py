@@ -154,6 +154,11 @@ SIGNATURES = {
                                      _P, _P, _P, _P, C.POINTER(C.c_uint32)]),
     'pgx_assoc_dev': (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P,
                                 C.c_size_t, _P, C.POINTER(C.c_uint32)]),
+    'pgx_allele_runs_workspace_bytes': (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_uint32]),
+    'pgx_allele_runs': (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint32, _P, _P, C.c_uint64, C.c_uint32, C.c_uint32, _P, C.c_uint32,
+                                  _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'pgx_allele_runs_dev': (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, _P, _P, _P, _P, _P,
+                                      _P, _P, _P, C.c_size_t, _P]),
     'pgx_cluster_greedy': (C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(ClusterParams), _P, _P, _P, _P,
                                      C.POINTER(C.c_uint32), C.POINTER(ClusterStats)]),
     'pgx_cluster_window_cap': (C.c_uint32, [C.POINTER(ClusterParams)]),
@@ -664,6 +669,51 @@ class Context(object):
                                   int(n_targets), flags, d_tp, d_incidence, d_block_of_row, d_rep_row, d_ws, int(ws_bytes),
                                   stream, C.byref(n_blocks)))
         return int(n_blocks.value)
+
+    # -- runs of allele rows (pangenome.validate_gene_table[_dense], extract_dominant_alleles) -----------------------------
+    RUNS_OUTPUTS = ('derived', 'diff', 'diff_per_genome', 'diff_per_run', 'total', 'best_allele', 'best_count')
+
+    def allele_runs(self, allele_rows, allele_genomes, n_alleles, n_genomes, run_start, gene_rows=None, gene_genomes=None,
+                    n_genes=0, gene_of_run=None, want=RUNS_OUTPUTS):
+        """({name: array for name in want}, (allele duplicates, gene duplicates)) of the runs [run_start[r], run_start[r + 1])
+        of the allele table's rows, compared with rows gene_of_run (-1: none) of the gene table when that is given (pgx.h:
+        pgx_allele_runs). 'derived' / 'diff' are uint64 [n_genomes, stride_words(n_runs)] bitmaps, 'diff_per_genome' /
+        'diff_per_run' / 'best_count' uint32, 'total' uint64, 'best_allele' int32. With duplicate coordinates nothing is
+        computed and the dict is None."""
+        a_rows, a_genomes = _coo_args(allele_rows, allele_genomes)
+        run_start = np.ascontiguousarray(run_start, dtype=np.uint32)
+        if run_start.ndim != 1 or run_start.size < 1:
+            raise ValueError('run_start must hold n_runs + 1 entries')
+        n_runs, n_genomes = run_start.size - 1, int(n_genomes)
+        g_rows = g_genomes = None
+        if gene_of_run is not None:
+            gene_of_run = np.ascontiguousarray(gene_of_run, dtype=np.int32)
+            if gene_of_run.shape != (n_runs,):
+                raise ValueError('gene_of_run must hold one entry per run')
+            g_rows, g_genomes = _coo_args(gene_rows if gene_rows is not None else [], gene_genomes if gene_genomes is not None else [])
+        unknown = set(want) - set(self.RUNS_OUTPUTS)
+        if unknown:
+            raise ValueError('unknown outputs %r' % sorted(unknown))
+        stride = lib().pgx_bitmap_stride_words(n_runs)
+        shapes = {'derived': ((n_genomes, stride), np.uint64), 'diff': ((n_genomes, stride), np.uint64),
+                  'diff_per_genome': (n_genomes, np.uint32), 'diff_per_run': (n_runs, np.uint32), 'total': (n_runs, np.uint64),
+                  'best_allele': (n_runs, np.int32), 'best_count': (n_runs, np.uint32)}
+        out = {k: np.zeros(*shapes[k]) for k in self.RUNS_OUTPUTS if k in want}
+        dup = np.zeros(2, dtype=np.uint64)
+        check(lib().pgx_allele_runs(self._h, _ptr(a_rows), _ptr(a_genomes), a_rows.size, int(n_alleles), _ptr(g_rows),
+                                    _ptr(g_genomes), 0 if g_rows is None else g_rows.size, int(n_genes), n_genomes,
+                                    _ptr(run_start), n_runs, _ptr(gene_of_run), *[_ptr(out.get(k)) for k in self.RUNS_OUTPUTS],
+                                    _ptr(dup)))
+        dups = (int(dup[0]), int(dup[1]))
+        return (None if any(dups) else out), dups
+
+    def allele_runs_dev(self, d_allele_bits, n_alleles, d_gene_bits, n_genes, n_genomes, d_run_start, n_runs, d_gene_of_run,
+                        d_derived, d_diff, d_diff_per_genome, d_diff_per_run, d_total, d_best_allele, d_best_count, d_ws,
+                        ws_bytes, stream=0):
+        """The same on device memory (raw device addresses, None for what is not wanted; synchronises `stream`, see pgx.h)."""
+        check(lib().pgx_allele_runs_dev(self._h, d_allele_bits, int(n_alleles), d_gene_bits, int(n_genes), int(n_genomes),
+                                        d_run_start, int(n_runs), d_gene_of_run, d_derived, d_diff, d_diff_per_genome,
+                                        d_diff_per_run, d_total, d_best_allele, d_best_count, d_ws, int(ws_bytes), stream))
 
     def pan_core(self, bits, n_genes, perms):
         perms = np.ascontiguousarray(perms, dtype=np.int32)

@@ -923,3 +923,274 @@ def build_downstream_pangenome(genome_data, allele_names, output_dir, limits=(-3
                                     include_fragments=include_fragments, max_overlap=max_overlap,
                                     fastasort_path=fastasort_path, output_format=output_format,
                                     fna_output_footer=fna_output_footer, overwrite_extract=overwrite_extract)
+
+
+# ---------------------------------------------------------------------------
+# gene table against allele table, dominant alleles (reference :1246-1330, :1812-1889, helpers :1919-2001):
+# runs of allele rows on the device bitmap (csrc/runs.hip)
+# ---------------------------------------------------------------------------
+def load_feature_table(feature_table):
+    """A path ending in .csv / .csv.gz is read with read_csv(index_col=0), one ending in .pickle / .pickle.gz with
+    read_pickle; any other string and anything that is not a string comes back as it is (reference :1919-1935)."""
+    if isinstance(feature_table, str):
+        import pandas as pd
+        lower = feature_table.lower()
+        if lower.endswith(('.csv', '.csv.gz')):
+            return pd.read_csv(feature_table, index_col=0)
+        if lower.endswith(('.pickle', '.pickle.gz')):
+            return pd.read_pickle(feature_table)
+    return feature_table
+
+
+def breakdown_feature_name(feature_name):
+    """(name, cluster type, cluster number, variant type, variant number) of a feature name; the last two are None for a
+    cluster-level name (reference :1972-1989).
+    Example 1: EsC_A123U56 -> ('EsC', 'A', 123, 'U', 56)
+    Example 2: PsA_T789 -> ('PsA', 'T', 789, None, None)"""
+    parts = feature_name.split('_')
+    name, footer = '_'.join(parts[:-1]), parts[-1]
+    for i in range(1, len(footer)):
+        if footer[i] in _VARIANT_LETTERS:
+            return name, footer[0], int(footer[1:i]), footer[i], int(footer[i + 1:])
+    return name, footer[0], int(footer[1:]), None, None
+
+
+_VARIANT_LETTERS = frozenset(VARIANT_TYPES.values())
+
+
+def trim_variant(feature_name):
+    """The name up to, not including, its right-most alphabetic character (the first character is never looked at); a name
+    without one comes back whole (reference :1992-2001)."""
+    for i in range(1, len(feature_name)):
+        if feature_name[-i].isalpha():
+            return feature_name[:-i]
+    return feature_name
+
+
+def _load_table(table):
+    """A table argument of the checks below: an .npz path is an LSDF, other paths go through load_feature_table."""
+    if isinstance(table, str) and table.lower().endswith('.npz'):
+        return sparse_utils.read_lsdf(table)
+    return load_feature_table(table)
+
+
+def _table_cells(table, who, notna):
+    """(rows int32, cols int32, index labels, column labels) of the cells of `table` that count as present.
+    LightSparseDataFrame: its stored entries, which must all be 1 (the rule of sparse_utils._screen_table: a stored zero or
+    any other value raises ValueError rather than being interpreted). pandas frame: with notna, every cell that is not NaN
+    (a 0.0 is present: dropna()); otherwise NaN and 0 are absent, 1 is present and any other value raises ValueError."""
+    if isinstance(table, sparse_utils.LightSparseDataFrame):
+        rows, cols, _, _ = sparse_utils._screen_table(table, who)
+        return rows, cols, np.asarray(table.index), np.asarray(table.columns)
+    if not (hasattr(table, 'index') and hasattr(table, 'columns') and hasattr(table, 'values')):
+        raise TypeError(who + ' takes a LightSparseDataFrame or a pandas DataFrame')
+    try:
+        values = np.asarray(table.values, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(who + ' needs a numeric table')
+    present = ~np.isnan(values)
+    if not notna:
+        ones = values == 1
+        if not np.all(ones | (values == 0) | ~present):
+            raise ValueError(who + ' needs a binary table (NaN or 0 = absent, 1 = present)')
+        present = ones
+    rows, cols = np.nonzero(present)
+    return rows.astype(np.int32), cols.astype(np.int32), np.asarray(table.index), np.asarray(table.columns)
+
+
+def _genes_of_alleles(allele_labels):
+    """__get_gene_from_allele__ of every label, as one array operation."""
+    labels = np.asarray(allele_labels, dtype=str)
+    if labels.size == 0:
+        return labels
+    return np.char.rpartition(labels, 'A')[:, 0]
+
+
+def _runs_by_name(gene_labels, allele_genes):
+    """validate_gene_table's grouping, whatever the order of the allele rows: one run per gene row (empty when the gene has
+    no allele), then one run without a gene row per gene name that occurs only among the alleles, in order of first
+    appearance. Returns (run names, run_start uint32, gene_of_run int32, new_row) where new_row[i] is the row allele i gets
+    in the gene-sorted table the device sees (a stable relabelling)."""
+    gene_labels = np.asarray(gene_labels, dtype=str)
+    n_genes = gene_labels.size
+    if np.unique(gene_labels).size != n_genes:
+        raise ValueError('validate_gene_table needs a gene table without repeated row labels')
+    names, first, inverse = np.unique(allele_genes, return_index=True, return_inverse=True)
+    order = np.argsort(gene_labels, kind='stable')
+    at = np.searchsorted(gene_labels[order], names)
+    known = (at < n_genes) & (gene_labels[order][np.minimum(at, max(n_genes - 1, 0))] == names) if n_genes else \
+        np.zeros(names.size, dtype=bool)
+    run_of_name = np.empty(names.size, dtype=np.int64)
+    run_of_name[known] = order[at[known]]
+    extra = np.flatnonzero(~known)
+    extra = extra[np.argsort(first[extra], kind='stable')]
+    run_of_name[extra] = n_genes + np.arange(extra.size)
+    run_of_allele = run_of_name[inverse.ravel()] if names.size else np.zeros(0, dtype=np.int64)
+    n_runs = n_genes + extra.size
+    run_start = np.zeros(n_runs + 1, dtype=np.int64)
+    np.cumsum(np.bincount(run_of_allele, minlength=n_runs), out=run_start[1:])
+    new_row = np.empty(run_of_allele.size, dtype=np.int64)
+    new_row[np.argsort(run_of_allele, kind='stable')] = np.arange(run_of_allele.size)
+    gene_of_run = np.full(n_runs, -1, dtype=np.int32)
+    gene_of_run[:n_genes] = np.arange(n_genes)
+    return np.concatenate([gene_labels, names[extra]]), run_start.astype(np.uint32), gene_of_run, new_row
+
+
+def _runs_in_order(names):
+    """The table-order grouping: maximal stretches of consecutive rows with the same name, so a name may recur.
+    Returns (run names, run_start uint32)."""
+    names = np.asarray(names, dtype=str)
+    if names.size == 0:
+        return names, np.zeros(1, dtype=np.uint32)
+    starts = np.concatenate([[0], np.flatnonzero(names[1:] != names[:-1]) + 1])
+    return names[starts], np.concatenate([starts, [names.size]]).astype(np.uint32)
+
+
+def _bitmap_row(bits, r):
+    """bool [n_genomes]: row r of a bitmap in the library's layout."""
+    return ((bits[:, r >> 6] >> np.uint64(r & 63)) & np.uint64(1)).astype(bool)
+
+
+def _allele_runs(ctx, who, **kwargs):
+    from . import _native
+    ctx = ctx or _native.default_context()
+    out, dups = ctx.allele_runs(**kwargs)
+    if any(dups):
+        raise ValueError(who + ' needs tables without duplicate entries')
+    return out
+
+
+def validate_gene_table(df_genes, df_alleles, log_group=1, ctx=None):
+    """Is the gene x genome table the OR of the allele x genome table's rows, gene by gene? Prints, per genome, the genes on
+    which the two tables disagree and returns their number (the reference, :1246-1277, returns None; its printed lines are
+    kept, the order of a set's elements apart). Alleles are grouped by __get_gene_from_allele__, whatever their order.
+    Both tables may be LightSparseDataFrames (what build_cds_pangenome returns), pandas frames or paths.
+    Presence: in a pandas frame every cell that is not NaN, so an explicit 0.0 is present (the reference's dropna()); in
+    an LSDF the stored entries, which must all be 1 -- the rule sparse_utils._screen_table applies: a stored zero or any
+    other value raises ValueError. The OR, the comparison and the counts run on the device (csrc/runs.hip); names are looked
+    up only for the genomes on which something differs. There is no CPU fallback."""
+    who = 'validate_gene_table'
+    g_rows, g_cols, gene_labels, genomes = _table_cells(_load_table(df_genes), who, notna=True)
+    a_rows, a_cols, allele_labels, allele_genomes = _table_cells(_load_table(df_alleles), who, notna=True)
+    if not np.array_equal(genomes, allele_genomes):                       # the reference reads dfa[genome] by label
+        column_of = {label: j for j, label in enumerate(allele_genomes.tolist())}
+        for genome in genomes.tolist():
+            if genome not in column_of:
+                raise KeyError(genome)
+        new_col = np.full(allele_genomes.size, -1, dtype=np.int64)
+        new_col[[column_of[g] for g in genomes.tolist()]] = np.arange(genomes.size)
+        keep = new_col[a_cols] >= 0
+        a_rows, a_cols = a_rows[keep], new_col[a_cols][keep]
+    run_names, run_start, gene_of_run, new_row = _runs_by_name(gene_labels, _genes_of_alleles(allele_labels))
+    print('Validating gene clusters...')
+    out = None
+    if genomes.size and run_names.size:
+        out = _allele_runs(ctx, who, allele_rows=new_row[a_rows], allele_genomes=a_cols, n_alleles=allele_labels.size,
+                           n_genomes=genomes.size, run_start=run_start, gene_rows=g_rows, gene_genomes=g_cols,
+                           n_genes=gene_labels.size, gene_of_run=gene_of_run, want=('diff', 'diff_per_genome'))
+    num_inconsistencies = 0
+    for g, genome in enumerate(genomes.tolist()):
+        if (g + 1) % log_group == 0:
+            print(g + 1, 'Testing', genome)
+        if out is not None and out['diff_per_genome'][g]:
+            word = np.flatnonzero(out['diff'][g])
+            runs = [int(w) * 64 + b for w in word for b in range(64) if (int(out['diff'][g, w]) >> b) & 1]
+            print('\tInconsistent:', set(run_names[runs].tolist()))
+            num_inconsistencies += len(runs)
+    print('Gene Table Inconsistencies:', num_inconsistencies)
+    return num_inconsistencies
+
+
+def validate_gene_table_dense(df_genes, df_alleles, ctx=None):
+    """The row-by-row form of the same check (reference :1280-1330): a run is a maximal stretch of consecutive allele rows
+    with the same gene name IN TABLE ORDER (a gene may recur), and the OR of its rows is compared with that gene's row,
+    genome by genome in column order. NaN and 0 are absent, 1 is present, any other value raises ValueError; a run whose
+    gene is missing from df_genes raises KeyError, as .loc does. The output is the reference's, its quirk included: after
+    `Inconsistent` it prints the name of the NEXT run (of the run itself for the last one), then the derived and the stored
+    row. Returns the number of inconsistent runs (the reference returns None). Runs on the device (csrc/runs.hip)."""
+    who = 'validate_gene_table_dense'
+    dfg = _load_table(df_genes)
+    g_rows, g_cols, gene_labels, genomes = _table_cells(dfg, who, notna=False)
+    a_rows, a_cols, allele_labels, allele_genomes = _table_cells(_load_table(df_alleles), who, notna=False)
+    if genomes.size != allele_genomes.size:
+        raise ValueError(who + ' compares the tables column by column: they must have as many')
+    run_names, run_start = _runs_in_order(_genes_of_alleles(allele_labels))
+    if run_names.size == 0:
+        raise KeyError(None)             # (the reference ends in dfg.loc[None] on a table without alleles)
+    row_of_gene = {}
+    for i, label in enumerate(gene_labels.tolist()):
+        row_of_gene.setdefault(label, i)
+    gene_of_run = np.empty(run_names.size, dtype=np.int32)
+    for r, label in enumerate(run_names.tolist()):
+        if label not in row_of_gene:
+            raise KeyError(label)
+        gene_of_run[r] = row_of_gene[label]
+    print('Validating gene clusters...')
+    out = _allele_runs(ctx, who, allele_rows=a_rows, allele_genomes=a_cols, n_alleles=allele_labels.size,
+                       n_genomes=genomes.size, run_start=run_start, gene_rows=g_rows, gene_genomes=g_cols,
+                       n_genes=gene_labels.size, gene_of_run=gene_of_run, want=('derived', 'diff', 'diff_per_run'))
+    n_runs = run_names.size
+    inconsistencies = 0
+    marks = set(np.flatnonzero(out['diff_per_run']).tolist())
+    marks.update(range(999, n_runs - 1, 1000))
+    for r in sorted(marks):
+        if out['diff_per_run'][r]:
+            has_gene = _bitmap_row(out['derived'], r)
+            print('Inconsistent', run_names[min(r + 1, n_runs - 1)])
+            print(has_gene)
+            if isinstance(dfg, sparse_utils.LightSparseDataFrame):
+                print((has_gene != _bitmap_row(out['diff'], r)).astype(np.float64))
+            else:
+                print(dfg.iloc[int(gene_of_run[r])].fillna(0).values)
+            inconsistencies += 1
+        if r < n_runs - 1 and (r + 1) % 1000 == 0:
+            print('\tTested', r + 1, 'clusters')
+    print('Gene Table Inconsistencies:', inconsistencies)
+    return inconsistencies
+
+
+def _gene_name_of_allele(allele):
+    terms = breakdown_feature_name(allele)
+    return terms[0] + '_' + terms[1] + str(terms[2])
+
+
+def extract_dominant_alleles(allele_table, allele_faa_file, dominant_out, ctx=None):
+    """The most common allele of every gene of an allele x genome table (reference :1812-1889). Runs are maximal stretches of
+    consecutive allele rows of one gene in table order; an allele's count is its row sum (NaN and 0 absent, 1 present, any
+    other value raises ValueError; an LSDF by its stored entries, all 1); the first allele with the largest count wins;
+    genes whose alleles occur nowhere are dropped. Returns df_dominant (index `gene`; columns dominant_allele, gene_count,
+    allele_count, the counts float64 as the reference produces them) and writes the dominant alleles' records of
+    allele_faa_file to dominant_out. allele_table may be a path (.npz: an LSDF; else load_feature_table). Sums and maxima
+    run on the device (csrc/runs.hip); the gene names are parsed from the labels on the host."""
+    import pandas as pd
+    who = 'extract_dominant_alleles'
+    print('Setting up allele table...')
+    a_rows, a_cols, allele_labels, genomes = _table_cells(_load_table(allele_table), who, notna=False)
+    print('Identifying dominant alleles...')
+    run_names, run_start = _runs_in_order([_gene_name_of_allele(a) for a in allele_labels.tolist()])
+    columns = ['gene', 'dominant_allele', 'gene_count', 'allele_count']
+    df_dominant = pd.DataFrame([], columns=columns)
+    if run_names.size and genomes.size:
+        out = _allele_runs(ctx, who, allele_rows=a_rows, allele_genomes=a_cols, n_alleles=allele_labels.size,
+                           n_genomes=genomes.size, run_start=run_start, want=('total', 'best_allele', 'best_count'))
+        kept = np.flatnonzero(out['total'] > 0)
+        if kept.size:
+            df_dominant = pd.DataFrame({'gene': run_names[kept].tolist(),
+                                        'dominant_allele': allele_labels[out['best_allele'][kept]].tolist(),
+                                        'gene_count': out['total'][kept].astype(np.float64),
+                                        'allele_count': out['best_count'][kept].astype(np.float64)}, columns=columns)
+    df_dominant = df_dominant.set_index('gene')
+    dominant_alleles = set(df_dominant.dominant_allele.values)
+    print('Found dominant alleles', df_dominant.shape, len(dominant_alleles))
+    print('Exporting dominant alleles...', end=' ')
+    alleles_written = 0
+    write_seq = False
+    with open(allele_faa_file, 'r') as f_allele, open(dominant_out, 'w+') as f_dom:
+        for line in f_allele:
+            if line[0] == '>':
+                write_seq = line[1:].strip() in dominant_alleles
+                alleles_written += write_seq
+            if write_seq:
+                f_dom.write(line)
+    print(alleles_written)
+    return df_dominant
