@@ -53,6 +53,7 @@
 #include <thread>
 #include <vector>
 
+#include "cluster_layout.h"
 #include "cluster_tables.h"
 #include "pgx_internal.h"
 
@@ -253,6 +254,166 @@ __global__ __launch_bounds__(256) void pack5_kernel(const uint8_t *__restrict__ 
             if (6 * w + t < L) x |= (uint32_t)s[6 * w + t] << (5u * t);
         dst[w] = x;
     }
+}
+
+// ----------------------------------------------------------------------------------------
+// prep on the device: length histogram, stable descending-length order, offsets
+// ----------------------------------------------------------------------------------------
+// The host needs the lengths only as a histogram: the sorted list is a run of equal lengths per bucket, and everything
+// it derives (n, totals, thresholds, size classes, offsets) follows from the counts. The order itself never leaves the
+// device before the outputs are written.
+// Up to kDevSortMaxLen letters per sequence the histogram and the (share, length) counters of the sort have a fixed,
+// small size; a call with a longer sequence (a handful of giant proteins exist) sorts on the host as a whole.
+constexpr uint32_t kDevSortMaxLen = 65535;
+constexpr uint32_t kHistLds = 4096;         // lengths below this are counted in LDS first (and reach the host with the first copy)
+constexpr uint32_t kSortShare = 1024;       // smallest share of the input per wave of the sort (a multiple of 64)
+constexpr uint32_t kSortCells = 4u << 20;   // most (length, share) counters: the shares grow until they fit
+constexpr uint32_t kScanTile = 2048;        // counters per workgroup of the scan
+enum : uint32_t { H_OVER = 0, H_MAX = 1, H_BINS = 4 };   // words in front of the histogram bins: lengths beyond the bound, longest
+
+// zero up to kClearSegs arrays of 32-bit words in one launch, and set one word to 1 (the prologue's small clears)
+constexpr int kClearSegs = 6;
+struct ClearArgs { uint32_t *p[kClearSegs]; uint32_t words[kClearSegs]; int n; uint32_t *one; };
+__global__ __launch_bounds__(256) void clear_kernel(ClearArgs a) {
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x, step = gridDim.x * 256u;
+    for (int s = 0; s < a.n; ++s)
+        for (uint32_t i = t; i < a.words[s]; i += step) a.p[s][i] = 0u;
+    if (a.one && t == 0) *a.one = 1u;
+}
+
+// hist[H_BINS + L] += sequences of L letters that pass min_length, L <= kDevSortMaxLen; hist[H_MAX] = longest of all,
+// hist[H_OVER] = number beyond the bound. A few large workgroups, so that the private LDS bins collect many counts
+// before they are flushed.
+__global__ __launch_bounds__(1024) void len_hist_kernel(const uint32_t *__restrict__ len, uint32_t n, int32_t min_length,
+                                                       uint32_t *__restrict__ hist) {
+    __shared__ uint32_t h[kHistLds];
+    for (uint32_t b = threadIdx.x; b < kHistLds; b += 1024u) h[b] = 0u;
+    __syncthreads();
+    uint32_t mx = 0, over = 0;
+    for (uint32_t i = blockIdx.x * 1024u + threadIdx.x; i < n; i += gridDim.x * 1024u) {
+        const uint32_t L = len[i];
+        mx = max(mx, L);
+        if (L > kDevSortMaxLen) { ++over; continue; }
+        if ((int32_t)L <= min_length) continue;
+        if (L < kHistLds) atomicAdd(&h[L], 1u);
+        else atomicAdd(&hist[H_BINS + L], 1u);
+    }
+    for (int d = 32; d > 0; d >>= 1) { mx = max(mx, (uint32_t)__shfl_xor(mx, d)); over += __shfl_xor(over, d); }
+    if ((threadIdx.x & 63u) == 0) {
+        if (mx) atomicMax(&hist[H_MAX], mx);
+        if (over) atomicAdd(&hist[H_OVER], over);
+    }
+    __syncthreads();
+    for (uint32_t b = threadIdx.x; b < kHistLds; b += 1024u)
+        if (h[b]) atomicAdd(&hist[H_BINS + b], h[b]);
+}
+
+// Stable counting sort by key = max_len - length. Share w = inputs [w * per, (w + 1) * per) belongs to one wave.
+// cnt[key * n_shares + w] counts the share's sequences of that key; scanned in this (key-major) order a counter is the
+// first sorted position of its share's run inside the key's run.
+__global__ __launch_bounds__(256) void sort_count_kernel(const uint32_t *__restrict__ len, uint32_t n, int32_t min_length,
+                                                        uint32_t max_len, uint32_t per, uint32_t n_shares,
+                                                        uint32_t *__restrict__ cnt) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t L = len[i];
+    if ((int32_t)L <= min_length || L > max_len) return;
+    atomicAdd(&cnt[(size_t)(max_len - L) * n_shares + i / per], 1u);
+}
+
+// exclusive scan of a[0..m) in place, two launches: sums[b] = total of tile b, then every tile scans itself behind the
+// tiles before it (at most kSortCells / kScanTile of them: each workgroup adds them up itself)
+__device__ __forceinline__ uint32_t block_sum_256(uint32_t s, uint32_t *ws) {
+    for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d);
+    if ((threadIdx.x & 63u) == 0) ws[threadIdx.x >> 6] = s;
+    __syncthreads();
+    s = ws[0] + ws[1] + ws[2] + ws[3];
+    __syncthreads();
+    return s;
+}
+__global__ __launch_bounds__(256) void tile_sum_kernel(const uint32_t *__restrict__ a, uint32_t m, uint32_t *__restrict__ sums) {
+    __shared__ uint32_t ws[4];
+    const uint32_t base = blockIdx.x * kScanTile;
+    uint32_t s = 0;
+    for (uint32_t j = threadIdx.x; j < kScanTile; j += 256u)
+        if (base + j < m) s += a[base + j];
+    s = block_sum_256(s, ws);
+    if (threadIdx.x == 0) sums[blockIdx.x] = s;
+}
+__global__ __launch_bounds__(256) void tile_scan_kernel(uint32_t *__restrict__ a, uint32_t m, const uint32_t *__restrict__ sums) {
+    __shared__ uint32_t ws[4];
+    uint32_t before = 0;
+    for (uint32_t j = threadIdx.x; j < blockIdx.x; j += 256u) before += sums[j];
+    before = block_sum_256(before, ws);
+    constexpr uint32_t kPer = kScanTile / 256u;   // consecutive counters per thread
+    const uint32_t i0 = blockIdx.x * kScanTile + threadIdx.x * kPer, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t v[kPer], t = 0;
+#pragma unroll
+    for (uint32_t u = 0; u < kPer; ++u) { v[u] = i0 + u < m ? a[i0 + u] : 0u; t += v[u]; }
+    uint32_t incl = t;
+    for (uint32_t d = 1; d < 64; d <<= 1) { const uint32_t x = __shfl_up(incl, d); if (lane >= d) incl += x; }
+    if (lane == 63u) ws[wave] = incl;
+    __syncthreads();
+    uint32_t run = before + incl - t;
+    for (uint32_t w = 0; w < wave; ++w) run += ws[w];
+#pragma unroll
+    for (uint32_t u = 0; u < kPer; ++u) { if (i0 + u < m) a[i0 + u] = run; run += v[u]; }
+}
+
+// One wave per share places its sequences 64 at a time, in input order: equal keys inside a step are ranked by
+// ballot, the first lane of each group takes the group's positions from the share's counter (the atomic returns before
+// the wave's next step reads the counter again: ties keep their input order).
+__global__ __launch_bounds__(256) void sort_place_kernel(const uint32_t *__restrict__ len, uint32_t n, int32_t min_length,
+                                                        uint32_t max_len, uint32_t per, uint32_t n_shares,
+                                                        uint32_t *__restrict__ cnt, uint32_t n_out,
+                                                        uint32_t *__restrict__ order) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t w = blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (w >= n_shares) return;
+    const uint64_t b = (uint64_t)w * per, e = min((uint64_t)n, b + per);
+    for (uint64_t i0 = b; i0 < e; i0 += 64) {
+        const uint64_t i = i0 + lane;
+        const uint32_t L = i < e ? len[i] : 0u;
+        const bool valid = i < e && (int32_t)L > min_length && L <= max_len;
+        const uint32_t key = valid ? max_len - L : 0u;
+        unsigned long long todo = __ballot(valid), mine = 0ull;
+        while (todo) {   // (uniform: one round per distinct key of the step)
+            const uint32_t k0 = __shfl(key, __ffsll(todo) - 1);
+            const unsigned long long m = __ballot(valid && key == k0);
+            if (valid && key == k0) mine = m;
+            todo &= ~m;
+        }
+        const int first = valid ? __ffsll(mine) - 1 : (int)lane;
+        uint32_t base = 0;
+        if (valid && (int)lane == first) base = atomicAdd(&cnt[(size_t)key * n_shares + w], (uint32_t)__popcll(mine));
+        base = __shfl(base, first);
+        const uint32_t pos = base + (uint32_t)__popcll(mine & ((1ull << lane) - 1ull));
+        if (valid && pos < n_out) order[pos] = (uint32_t)i;
+    }
+}
+
+// lengths, residue offsets and packed-word offsets of the sorted list from the run tables: run r = the sequences of
+// max_len - r letters, first at sorted position run_pos[r], residue offset run_off[r], packed word run_pk[r]
+// (n_runs + 1 entries each, the last = the totals). The second half (both strands) repeats the first behind it.
+__global__ __launch_bounds__(256) void layout_kernel(const uint64_t *__restrict__ run_off, const uint32_t *__restrict__ run_pos,
+                                                    const uint32_t *__restrict__ run_pk, uint32_t n_runs, uint32_t max_len,
+                                                    uint32_t n, uint32_t nv, uint32_t *__restrict__ len,
+                                                    uint64_t *__restrict__ off, uint32_t *__restrict__ pk_off) {
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (k > nv) return;
+    const uint64_t total = run_off[n_runs];
+    const uint32_t total_pk = run_pk[n_runs];
+    if (k == nv) { off[k] = (uint64_t)(nv / n) * total; pk_off[k] = (nv / n) * total_pk; return; }
+    const uint32_t half = k >= n ? 1u : 0u, kk = half ? k - n : k;
+    uint32_t lo = 0, hi = n_runs;   // run_pos[lo] <= kk < run_pos[hi]; empty runs share their start with the run behind them
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (run_pos[mid] <= kk) lo = mid; else hi = mid;
+    }
+    const uint32_t L = max_len - lo, j = kk - run_pos[lo];
+    len[k] = L;
+    off[k] = half * total + run_off[lo] + (uint64_t)j * L;
+    pk_off[k] = half * total_pk + run_pk[lo] + j * ((L + 5u) / 6u);
 }
 
 // ----------------------------------------------------------------------------------------
@@ -2441,90 +2602,156 @@ static int cluster_greedy_impl(pgx_ctx *ctx, const uint8_t *d_residues, const ui
     if (n_in == 0) { if (stats) *stats = S; return PGX_OK; }
 
     // ---- A.2 / A.3: letters -> indices, stable descending-length order ---------------------
-    // The GPU counts letters and later gathers/encodes the residues; the O(n) bookkeeping
-    // (counting sort by length, offsets, thresholds) is done on the host from the lengths.
+    // The GPU counts letters, orders the sequences and lays them out; the host sees the lengths as a histogram (one
+    // small copy, one synchronisation) and derives its O(longest length) bookkeeping from that. Its per-sequence arrays
+    // are filled behind the enqueued device work.
+    DevBuf d_res, d_off, d_len, d_wcode, d_wmult, d_wcnt, d_aa1, d_aas, d_aan, d_lines, d_pool[2], d_idx,
+        d_newbits, d_touched, d_first, d_best_own, d_rcvis, d_counters, d_visits, d_pairsW, d_pairsK, d_blk_list,
+        d_ulist, d_new_list, d_flags, d_gscratch, d_order, d_list, d_gather, d_pk, d_pkoff,
+        d_counters2, d_best2, d_flags2, d_pairsW2, d_gscratch2,   // second set of a window's own state (see `overlap`)
+        d_thr, d_hugewords, d_xsend, d_xrecv,
+        d_hist, d_sortcnt, d_tilesum, d_runs;                     // the prologue's histogram, sort counters, run tables
+    {   // all of them live in the context's workspace (slots 1..)
+        DevBuf *all[] = {&d_res, &d_off, &d_len, &d_wcode, &d_wmult, &d_wcnt, &d_aa1, &d_aas, &d_aan, &d_lines,
+                         &d_pool[0], &d_pool[1], &d_idx, &d_newbits, &d_touched, &d_first, &d_best_own, &d_rcvis,
+                         &d_counters, &d_visits, &d_pairsW, &d_pairsK, &d_blk_list, &d_ulist, &d_new_list, &d_flags,
+                         &d_gscratch, &d_order, &d_list, &d_gather, &d_pk, &d_pkoff,
+                         &d_counters2, &d_best2, &d_flags2, &d_pairsW2, &d_gscratch2, &d_thr, &d_hugewords,
+                         &d_xsend, &d_xrecv, &d_hist, &d_sortcnt, &d_tilesum, &d_runs};
+        int sl = 1;
+        for (DevBuf *b : all) { b->ctx = ctx; b->slot = sl++; }
+    }
+    uint32_t n_codes = 1;
+    for (int t = 0; t < P->word_len; ++t) n_codes *= nt ? 4u : (uint32_t)kNAA1;
+    static_assert(kSegs == 4, "eight codes per word of the round's map");
+    const uint32_t bm_words = (n_codes / 8 + 2 + 3) & ~3u;   // words of the round's map of touched codes
+    const bool overlap = !nt && !std::getenv("PGX_NO_OVERLAP");   // consecutive windows on two streams, see below
     DevBuf d_in_len;
     d_in_len.ctx = ctx; d_in_len.slot = 0;
     PGX_HIP(d_in_len.alloc((size_t)n_in * 4));
+    constexpr uint32_t kHistWords = H_BINS + kDevSortMaxLen + 1;
+    PGX_HIP(d_hist.alloc((size_t)kHistWords * 4));
+    PGX_HIP(d_idx.alloc(16));
+    PGX_HIP(d_newbits.alloc(2 * (size_t)bm_words * 4 + 16));          // two maps, used by alternate append rounds
+    PGX_HIP(d_counters.alloc(C_COUNT * 4));
+    PGX_HIP(d_visits.alloc(8));
+    if (overlap) PGX_HIP(d_counters2.alloc(C_COUNT * 4));
+    {   // the call's small clears in one launch (a hipMemsetAsync each left the stream idle in between): the histogram,
+        // the two round maps, the counters of both window sets, the visit counter; pool word 0 is never an array
+        // (ovf == 0 means "no overflow array"), so the pool's cursor starts at 1
+        ClearArgs ca{};
+        auto seg = [&](DevBuf &b, size_t words) { ca.p[ca.n] = b.as<uint32_t>(); ca.words[ca.n] = (uint32_t)words; ++ca.n; };
+        seg(d_hist, kHistWords);
+        seg(d_newbits, 2 * (size_t)bm_words);
+        seg(d_counters, C_COUNT);
+        seg(d_visits, 2);
+        if (overlap) seg(d_counters2, C_COUNT);
+        ca.one = d_idx.as<uint32_t>();
+        clear_kernel<<<1024, 256, 0, st>>>(ca);
+        LAUNCH_CHECK();
+    }
     {
         ProfScope prof(ctx, "seq_len_kernel", st);
         seq_len_kernel<<<(n_in + 3) / 4, 256, 0, st>>>(d_residues, d_offsets, n_in, total_in, d_in_len.as<uint32_t>());
+        len_hist_kernel<<<std::min(64u, (n_in + 1023u) / 1024u), 1024, 0, st>>>(d_in_len.as<uint32_t>(), n_in, P->min_length,
+                                                                               d_hist.as<uint32_t>());
     }
     LAUNCH_CHECK();
     // (the per-sequence host arrays live in the context's scratch: no allocation, page faults or frees per call)
-    HostVec<uint32_t> in_len(ctx, 0, n_in);
-    PGX_REQUIRE(in_len.ok(), "out of host memory");
-    PGX_HIP(hipMemcpyAsync(in_len.data(), d_in_len.p, (size_t)n_in * 4, hipMemcpyDeviceToHost, st));
+    HostVec<uint32_t> h_hist(ctx, 6, kHistWords);
+    PGX_REQUIRE(h_hist.ok(), "out of host memory");
+    PGX_HIP(hipMemcpyAsync(h_hist.data(), d_hist.p, (size_t)(H_BINS + kHistLds) * 4, hipMemcpyDeviceToHost, st));
     PGX_HIP(hipStreamSynchronize(st));
-    phase("  seq_len kernel + copy");
-    uint32_t max_len = 0;
-    {
-        std::vector<uint32_t> mx(nth, 0u);
-        parallel_for(n_in, nth, [&](unsigned t, size_t b, size_t e) {
-            uint32_t m = 0;
-            for (size_t i = b; i < e; ++i) m = std::max(m, in_len[i]);
-            mx[t] = m;
-        });
-        for (uint32_t m : mx) max_len = std::max(max_len, m);
+    // PGX_HOST_PROLOGUE=1 takes the host's sort for any input (for comparisons)
+    const bool dev_sort = h_hist[H_OVER] == 0 && !std::getenv("PGX_HOST_PROLOGUE");
+    uint32_t max_len = h_hist[H_MAX];
+    if (dev_sort && max_len >= kHistLds) {   // (rare: the bins the first copy left out)
+        PGX_HIP(hipMemcpyAsync(h_hist.data() + H_BINS + kHistLds, d_hist.as<uint32_t>() + H_BINS + kHistLds,
+                               (size_t)(max_len + 1 - kHistLds) * 4, hipMemcpyDeviceToHost, st));
+        PGX_HIP(hipStreamSynchronize(st));
     }
-    if (max_len > kMaxLen) {
-        pgx_set_error("pgx_cluster_greedy: sequence of %u residues exceeds the supported maximum %u", max_len, kMaxLen);
-        return PGX_ERR_CAPACITY;
-    }
-    // stable counting sort by descending length: a histogram per thread over its share of the input, then
-    // every thread places its share behind the shares before it
-    const size_t n_bkt = (size_t)max_len + 2;
-    std::vector<uint32_t> bucket(n_bkt * nth, 0);   // [t][l]
-    parallel_for(n_in, nth, [&](unsigned t, size_t b, size_t e) {
-        uint32_t *h = bucket.data() + n_bkt * t;
-        for (size_t i = b; i < e; ++i)
-            if ((int)in_len[i] > P->min_length) h[max_len - in_len[i]]++;
-    });
+    phase("  seq_len + histogram + copy");
+    const uint32_t *len_hist = h_hist.data() + H_BINS;   // [L] = sequences of L letters that pass min_length
     uint32_t n = 0;
-    for (size_t l = 0; l < n_bkt; ++l)
-        for (unsigned t = 0; t < nth; ++t) { const uint32_t c = bucket[n_bkt * t + l]; bucket[n_bkt * t + l] = n; n += c; }
-    HostVec<uint32_t> order(ctx, 1, n);
-    PGX_REQUIRE(order.ok(), "out of host memory");
-    parallel_for(n_in, nth, [&](unsigned t, size_t b, size_t e) {
-        uint32_t *h = bucket.data() + n_bkt * t;
-        for (size_t i = b; i < e; ++i)
-            if ((int)in_len[i] > P->min_length) order[h[max_len - in_len[i]]++] = (uint32_t)i;
-    });
+    HostVec<uint32_t> order(ctx, 1, dev_sort ? 0 : n_in);   // (device sort: bound to n entries below)
+    std::vector<uint32_t> host_hist;
+    if (dev_sort) {
+        for (uint32_t L = 0; L <= max_len; ++L) n += len_hist[L];
+    } else {
+        // a sequence beyond kDevSortMaxLen: the lengths come to the host, which sorts them and uploads the order
+        HostVec<uint32_t> in_len(ctx, 0, n_in);
+        PGX_REQUIRE(in_len.ok() && order.ok(), "out of host memory");
+        PGX_HIP(hipMemcpyAsync(in_len.data(), d_in_len.p, (size_t)n_in * 4, hipMemcpyDeviceToHost, st));
+        PGX_HIP(hipStreamSynchronize(st));
+        max_len = 0;
+        {
+            std::vector<uint32_t> mx(nth, 0u);
+            parallel_for(n_in, nth, [&](unsigned t, size_t b, size_t e) {
+                uint32_t m = 0;
+                for (size_t i = b; i < e; ++i) m = std::max(m, in_len[i]);
+                mx[t] = m;
+            });
+            for (uint32_t m : mx) max_len = std::max(max_len, m);
+        }
+        if (max_len > kMaxLen) {
+            pgx_set_error("pgx_cluster_greedy: sequence of %u residues exceeds the supported maximum %u", max_len, kMaxLen);
+            return PGX_ERR_CAPACITY;
+        }
+        // stable counting sort by descending length: a histogram per thread over its share of the input, then
+        // every thread places its share behind the shares before it
+        const size_t n_bkt = (size_t)max_len + 2;
+        std::vector<uint32_t> bucket(n_bkt * nth, 0);   // [t][l]
+        parallel_for(n_in, nth, [&](unsigned t, size_t b, size_t e) {
+            uint32_t *h = bucket.data() + n_bkt * t;
+            for (size_t i = b; i < e; ++i)
+                if ((int)in_len[i] > P->min_length) h[max_len - in_len[i]]++;
+        });
+        host_hist.assign((size_t)max_len + 1, 0u);
+        for (size_t l = 0; l <= max_len; ++l)
+            for (unsigned t = 0; t < nth; ++t) {
+                const uint32_t c = bucket[n_bkt * t + l];
+                bucket[n_bkt * t + l] = n; n += c; host_hist[max_len - l] += c;
+            }
+        parallel_for(n_in, nth, [&](unsigned t, size_t b, size_t e) {
+            uint32_t *h = bucket.data() + n_bkt * t;
+            for (size_t i = b; i < e; ++i)
+                if ((int)in_len[i] > P->min_length) order[h[max_len - in_len[i]]++] = (uint32_t)i;
+        });
+        len_hist = host_hist.data();
+    }
     if (n == 0) { if (stats) *stats = S; return PGX_OK; }
     PGX_REQUIRE(n < (1u << 30), "too many sequences for the index entries (30 bits)");
     uint32_t mshift = 8;                         // smallest field that holds n (and the strike-out value above it)
     while ((1u << mshift) <= n) ++mshift;
+    if (dev_sort) order = HostVec<uint32_t>(ctx, 1, n);   // (arrives behind the device's sort, read when outputs are written)
 
-    phase("  counting sort");
     // sequences n .. 2n-1 are the reverse complements (nucleotides, both strands)
     const uint32_t nv = both ? 2 * n : n;
     HostVec<uint64_t> h_off(ctx, 2, (size_t)nv + 1);
     HostVec<uint32_t> h_len(ctx, 3, nv);
-    PGX_REQUIRE(h_off.ok() && h_len.ok(), "out of host memory");
-    HostVec<uint32_t> h_pkoff(ctx, 4, (size_t)nv + 1);
-    PGX_REQUIRE(h_pkoff.ok(), "out of host memory");
-    // lengths in sorted order; residue and packed-word offsets = prefix sums (per-share sums first, then the shares)
-    std::vector<uint64_t> sum_len(nth + 1, 0), sum_pk(nth + 1, 0);
-    parallel_for(nv, nth, [&](unsigned t, size_t b, size_t e) {
-        uint64_t sl = 0, sp = 0;
-        for (size_t k = b; k < e; ++k) {
-            const uint32_t L = in_len[order[k < n ? k : k - n]];
-            h_len[k] = L; sl += L; sp += (L + 5) / 6;
-        }
-        sum_len[t + 1] = sl; sum_pk[t + 1] = sp;
-    });
-    for (unsigned t = 0; t < nth; ++t) { sum_len[t + 1] += sum_len[t]; sum_pk[t + 1] += sum_pk[t]; }
-    const uint64_t total = sum_len[nth];
-    if (sum_pk[nth] > 0xFFFFFFF0ull) { pgx_set_error("pgx_cluster_greedy: too many residues for 32-bit packed offsets"); return PGX_ERR_CAPACITY; }
-    h_off[0] = 0; h_pkoff[0] = 0;
-    parallel_for(nv, nth, [&](unsigned t, size_t b, size_t e) {
-        uint64_t so = sum_len[t], sp = sum_pk[t];
-        for (size_t k = b; k < e; ++k) {
-            so += h_len[k]; sp += (h_len[k] + 5) / 6;
-            h_off[k + 1] = so; h_pkoff[k + 1] = (uint32_t)sp;
-        }
-    });
-    phase("lengths + order");
+    PGX_REQUIRE(order.ok() && h_off.ok() && h_len.ok(), "out of host memory");
+    // The sorted list is one run of equal lengths per histogram bucket: run r holds the sequences of max_len - r
+    // letters. Its first sorted position, residue offset and packed-word offset are prefix sums over the buckets; inside
+    // a run offsets advance by the length. The device (layout_kernel) and the host (below, behind the enqueued work)
+    // expand the same tables.
+    const uint32_t n_runs = max_len + 1;
+    HostVec<uint64_t> h_runs(ctx, 7, 2 * ((size_t)n_runs + 1));
+    PGX_REQUIRE(h_runs.ok(), "out of host memory");
+    uint64_t *const run_off = h_runs.data();
+    uint32_t *const run_pos = reinterpret_cast<uint32_t *>(run_off + n_runs + 1), *const run_pk = run_pos + n_runs + 1;
+    if ((both ? 2 : 1) * build_run_tables(len_hist, max_len, run_off, run_pos, run_pk) > 0xFFFFFFF0ull) {
+        pgx_set_error("pgx_cluster_greedy: too many residues for 32-bit packed offsets");
+        return PGX_ERR_CAPACITY;
+    }
+    const uint64_t total = (both ? 2 : 1) * run_off[n_runs];   // residues and packed words of all nv sequences
+    const uint64_t total_pk = (uint64_t)(both ? 2 : 1) * run_pk[n_runs];
+    auto fill_host_layout = [&]() {   // h_len, h_off from the run tables
+        parallel_for(nv, nth, [&](unsigned, size_t b, size_t e) {
+            expand_runs(run_off, run_pos, max_len, n, b, e, h_len.data(), h_off.data());
+        });
+        h_off[nv] = total;
+    };
+    phase(dev_sort ? "  run tables" : "  host sort + run tables");
     // per-query thresholds in double, exactly as the sequential rule computes them
     // They depend on the length only: one small table per threshold (host, in double), expanded per sequence on
     // the device (thresholds_kernel) instead of three host passes and three uploads of n integers.
@@ -2544,19 +2771,13 @@ static int cluster_greedy_impl(pgx_ctx *ctx, const uint8_t *d_residues, const ui
                 t_aan[L] = (int)(P->aan_cutoff * (double)len);
             }
         }
-        std::vector<uint8_t> bad(nth, 0);
-        parallel_for(n, nth, [&](unsigned t, size_t b, size_t e) {   // (the lengths that occur: run boundaries of the sorted list)
-            for (size_t k = b; k < e; ++k)
-                if ((k == b || h_len[k] != h_len[k - 1]) && t_aas[h_len[k]] < 1) bad[t] = 1;
-        });
-        for (uint8_t b : bad) PGX_REQUIRE(!b, "aas_cutoff too small: every sequence needs required_aas >= 1");
-        S.sum_len_queries = h_off[n];
+        for (uint32_t L = 0; L <= max_len; ++L)   // (the lengths that occur)
+            PGX_REQUIRE(!(len_hist[L] && t_aas[L] < 1), "aas_cutoff too small: every sequence needs required_aas >= 1");
+        S.sum_len_queries = run_off[n_runs];
     }
     S.n_clustered = n;
 
     // ---- device buffers ------------------------------------------------------------------
-    uint32_t n_codes = 1;
-    for (int t = 0; t < P->word_len; ++t) n_codes *= nt ? 4u : (uint32_t)kNAA1;
     const uint32_t window_cap = pgx_cluster_window_cap(P);           // queries per window
     PGX_REQUIRE(!exchanging || window_cap <= PGX_EXCHANGE_KEYS, "window larger than PGX_EXCHANGE_KEYS");
     uint32_t pair_cap = 4u << 20;  // grows per window for nucleotides, whose word filter passes almost every pair
@@ -2600,27 +2821,6 @@ static int cluster_greedy_impl(pgx_ctx *ctx, const uint8_t *d_residues, const ui
         C.begin[C.n] = q;
         return q;
     };
-    uint64_t max_window_words = 0;
-    uint32_t max_chunks = 1;   // the tag records are only as long as some window has chunks
-    {
-        Chunks C;
-        size_t nf = 0;
-        for (uint32_t b0 = 0, nbw; b0 < n; b0 += nbw) {
-            while (nf < flush_at.size() && flush_at[nf] <= b0) ++nf;
-            nbw = form_window(b0, C, nf < flush_at.size() ? flush_at[nf] : n);
-            max_window_words = std::max<uint64_t>(max_window_words, h_off[b0 + nbw] - h_off[b0]);
-            max_chunks = std::max(max_chunks, C.n);
-        }
-        if (!flush_at.empty())   // (the sweeps' windows start anywhere: no window holds more than the window_cap longest sequences)
-            max_window_words = std::max<uint64_t>(max_window_words, h_off[std::min(n, window_cap)]);
-    }
-    // The chunk volume adapts (cur_frac below), so later windows are not the ones of this scan: bound a window's words
-    // independently of the partition -- no more than the window_cap longest sequences, no more than kMaxChunks
-    // chunks of the largest volume (a chunk closes before it would exceed that, or holds one sequence).
-    if (chunking && flush_at.empty())
-        max_window_words = std::max<uint64_t>(max_window_words,
-            std::min<uint64_t>(h_off[std::min(n, window_cap)], (uint64_t)kMaxChunks * std::max<uint64_t>(chunk_words, max_len)));
-    PGX_REQUIRE(max_window_words < 0xFFFFFFF0ull, "window too large");
     const bool need_gscratch = (uint64_t)max_len * 2 > kDiagLdsSmall;
     const uint32_t packed_len = nt ? kPackedLenNt : kPackedLenAa;   // queries beyond this: 64-bit histogram cells
     const uint32_t gs_cells = (max_len + 64u) & ~63u;
@@ -2630,47 +2830,20 @@ static int cluster_greedy_impl(pgx_ctx *ctx, const uint8_t *d_residues, const ui
     const uint32_t diag_grid = (uint32_t)std::max<uint64_t>(64, std::min<uint64_t>(8192, (4ull << 30) / ((uint64_t)gs_stride * 4)));
     const uint32_t align_grid = 1024;
 
-    DevBuf d_res, d_off, d_len, d_wcode, d_wmult, d_wcnt, d_aa1, d_aas, d_aan, d_lines, d_pool[2], d_idx,
-        d_newbits, d_touched, d_first, d_best_own, d_rcvis, d_counters, d_visits, d_pairsW, d_pairsK, d_blk_list,
-        d_ulist, d_new_list, d_flags, d_gscratch, d_order, d_list, d_gather, d_pk, d_pkoff,
-        d_counters2, d_best2, d_flags2, d_pairsW2, d_gscratch2,   // second set of a window's own state (see `overlap`)
-        d_thr, d_hugewords, d_xsend, d_xrecv;
-    {   // all of them live in the context's workspace (slots 1..)
-        DevBuf *all[] = {&d_res, &d_off, &d_len, &d_wcode, &d_wmult, &d_wcnt, &d_aa1, &d_aas, &d_aan, &d_lines,
-                         &d_pool[0], &d_pool[1], &d_idx, &d_newbits, &d_touched, &d_first, &d_best_own, &d_rcvis,
-                         &d_counters, &d_visits, &d_pairsW, &d_pairsK, &d_blk_list, &d_ulist, &d_new_list, &d_flags,
-                         &d_gscratch, &d_order, &d_list, &d_gather, &d_pk, &d_pkoff,
-                         &d_counters2, &d_best2, &d_flags2, &d_pairsW2, &d_gscratch2, &d_thr, &d_hugewords,
-                         &d_xsend, &d_xrecv};
-        int sl = 1;
-        for (DevBuf *b : all) { b->ctx = ctx; b->slot = sl++; }
-    }
-    phase("thresholds + offsets");
     PGX_HIP(d_res.alloc(total + 16));
     PGX_HIP(d_off.alloc(((size_t)nv + 1) * 8));
     PGX_HIP(d_len.alloc((size_t)nv * 4));
     PGX_HIP(d_wcode.alloc((total + 16) * 4));
     PGX_HIP(d_wmult.alloc((total + 16) * 2));
     PGX_HIP(d_wcnt.alloc((size_t)nv * 4));
-    PGX_HIP(d_pk.alloc(((size_t)h_pkoff[nv] + 16) * 4));
+    PGX_HIP(d_pk.alloc(((size_t)total_pk + 16) * 4));
     PGX_HIP(d_pkoff.alloc(((size_t)nv + 1) * 4));
-    PGX_HIP(hipMemcpyAsync(d_pkoff.p, h_pkoff.data(), ((size_t)nv + 1) * 4, hipMemcpyHostToDevice, st));
     PGX_HIP(d_aa1.alloc((size_t)n * 4));
     PGX_HIP(d_aas.alloc((size_t)n * 4));
     PGX_HIP(d_aan.alloc((size_t)n * 4));
     // the word index: all lines empty (one memset of n_codes * 128 B per call, e.g. 523 MB for protein 5-mers)
     PGX_HIP(d_lines.alloc((size_t)n_codes * sizeof(IndexLine)));
     PGX_HIP(hipMemsetAsync(d_lines.p, 0, (size_t)n_codes * sizeof(IndexLine), st));
-    PGX_HIP(d_idx.alloc(16));
-    static_assert(kSegs == 4, "eight codes per word of the round's map");
-    const uint32_t bm_words = (n_codes / 8 + 2 + 3) & ~3u;   // words of the round's map of touched codes
-    PGX_HIP(d_newbits.alloc(2 * (size_t)bm_words * 4 + 16));          // two maps, used by alternate append rounds
-    PGX_HIP(hipMemsetAsync(d_newbits.p, 0, 2 * (size_t)bm_words * 4, st));
-    PGX_HIP(d_touched.alloc((max_window_words + 16) * sizeof(Deferred)));   // entries set aside by an append round
-    if (chunking && n > window_cap / 2) max_chunks = kMaxChunks;   // (smaller chunks later may need all of them)
-    uint32_t tag_stride = 1;   // first-open tags: one record of tag_stride >= max_chunks words per code
-    while (tag_stride < max_chunks) tag_stride *= 2;
-    PGX_HIP(d_first.alloc((size_t)tag_stride * n_codes * 4 + 16));
     PGX_HIP(d_best_own.alloc((size_t)window_cap * 8));
     PGX_HIP(d_rcvis.alloc((size_t)window_cap * 8));
     PGX_HIP(d_blk_list.alloc((size_t)kBlockCap * 4));
@@ -2679,9 +2852,6 @@ static int cluster_greedy_impl(pgx_ctx *ctx, const uint8_t *d_residues, const ui
     PGX_HIP(d_flags.alloc(4 * (size_t)window_cap));  // done, in-block, has-candidate, accepted
     PGX_HIP(d_list.alloc((size_t)pair_cap_k * 4));
     PGX_HIP(d_gather.alloc((size_t)pair_cap_k * sizeof(Pair)));
-    PGX_HIP(d_counters.alloc(C_COUNT * 4));
-    PGX_HIP(hipMemsetAsync(d_counters.p, 0, C_COUNT * 4, st));
-    PGX_HIP(d_visits.alloc(8));
     PGX_HIP(d_pairsW.alloc((size_t)pair_cap * sizeof(Pair)));
     PGX_HIP(d_pairsK.alloc((size_t)pair_cap_k * sizeof(Pair)));
     if (need_gscratch) PGX_HIP(d_gscratch.alloc((size_t)diag_grid * gs_stride * 4));
@@ -2693,10 +2863,7 @@ static int cluster_greedy_impl(pgx_ctx *ctx, const uint8_t *d_residues, const ui
     // A few hundred pairs per evaluation keep a 60-us dependent chain per alignment on the path otherwise.
     // (Record-sharded mode too: the exchange buffers have one slot per window in flight, and every process enqueues its
     // collectives in the same order because the host logic is the same function of replicated results.)
-    const bool overlap = !nt && !std::getenv("PGX_NO_OVERLAP");
     if (overlap) {
-        PGX_HIP(d_counters2.alloc(C_COUNT * 4));
-        PGX_HIP(hipMemsetAsync(d_counters2.p, 0, C_COUNT * 4, st));
         if (!exchanging) PGX_HIP(d_best2.alloc((size_t)window_cap * 8));
         PGX_HIP(d_flags2.alloc(4 * (size_t)window_cap));
         PGX_HIP(d_pairsW2.alloc((size_t)pair_cap * sizeof(Pair)));
@@ -2718,15 +2885,41 @@ static int cluster_greedy_impl(pgx_ctx *ctx, const uint8_t *d_residues, const ui
         pool_cap = want;
         return PGX_OK;
     };
-    {
-        const uint32_t one = 1u;   // pool word 0 is never an array: ovf == 0 means "no overflow array"
-        PGX_HIP(hipMemcpyAsync(d_idx.p, &one, 4, hipMemcpyHostToDevice, st));
-    }
-
     PGX_HIP(d_order.alloc((size_t)n * 4));
-    PGX_HIP(hipMemcpyAsync(d_order.p, order.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
-    PGX_HIP(hipMemcpyAsync(d_off.p, h_off.data(), ((size_t)nv + 1) * 8, hipMemcpyHostToDevice, st));
-    PGX_HIP(hipMemcpyAsync(d_len.p, h_len.data(), (size_t)nv * 4, hipMemcpyHostToDevice, st));
+    if (dev_sort) {
+        // stable counting sort on the device: a share of the input per wave, the smallest that keeps the
+        // (length, share) counters within kSortCells
+        uint32_t per = kSortShare;
+        while ((uint64_t)((n_in + per - 1) / per) * n_runs > kSortCells) per *= 2;
+        const uint32_t n_shares = (n_in + per - 1) / per, cells = n_shares * n_runs, tiles = (cells + kScanTile - 1) / kScanTile;
+        PGX_HIP(d_sortcnt.alloc((size_t)cells * 4));
+        PGX_HIP(d_tilesum.alloc((size_t)tiles * 4));
+        uint32_t *const cnt = d_sortcnt.as<uint32_t>(), *const in_len = d_in_len.as<uint32_t>();
+        ProfScope prof(ctx, "length_sort_kernels", st);
+        ClearArgs ca{};
+        ca.p[0] = cnt; ca.words[0] = cells; ca.n = 1;
+        clear_kernel<<<std::min(2048u, (cells + 255u) / 256u), 256, 0, st>>>(ca);
+        sort_count_kernel<<<(n_in + 255) / 256, 256, 0, st>>>(in_len, n_in, P->min_length, max_len, per, n_shares, cnt);
+        tile_sum_kernel<<<tiles, 256, 0, st>>>(cnt, cells, d_tilesum.as<uint32_t>());
+        tile_scan_kernel<<<tiles, 256, 0, st>>>(cnt, cells, d_tilesum.as<uint32_t>());
+        sort_place_kernel<<<(n_shares + 3) / 4, 256, 0, st>>>(in_len, n_in, P->min_length, max_len, per, n_shares, cnt, n,
+                                                              d_order.as<uint32_t>());
+        LAUNCH_CHECK();
+        // (the host reads the order when it writes a window's outputs, behind kernels enqueued after this copy)
+        PGX_HIP(hipMemcpyAsync(order.data(), d_order.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    } else {
+        PGX_HIP(hipMemcpyAsync(d_order.p, order.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+    }
+    {   // lengths, offsets and packed offsets of the sorted list, both halves, from the run tables
+        const size_t runs_bytes = 2 * ((size_t)n_runs + 1) * 8;
+        PGX_HIP(d_runs.alloc(runs_bytes));
+        PGX_HIP(hipMemcpyAsync(d_runs.p, h_runs.data(), runs_bytes, hipMemcpyHostToDevice, st));
+        const uint64_t *const dr_off = d_runs.as<uint64_t>();
+        const uint32_t *const dr_pos = reinterpret_cast<const uint32_t *>(dr_off + n_runs + 1), *const dr_pk = dr_pos + n_runs + 1;
+        layout_kernel<<<nv / 256 + 1, 256, 0, st>>>(dr_off, dr_pos, dr_pk, n_runs, max_len, n, nv, d_len.as<uint32_t>(),
+                                                    d_off.as<uint64_t>(), d_pkoff.as<uint32_t>());
+        LAUNCH_CHECK();
+    }
     {
         ProfScope prof(ctx, "encode_gather_kernel", st);
         encode_gather_kernel<<<(n + 3) / 4, 256, 0, st>>>(d_residues, d_offsets, d_order.as<uint32_t>(),
@@ -2745,16 +2938,11 @@ static int cluster_greedy_impl(pgx_ctx *ctx, const uint8_t *d_residues, const ui
                                                           d_aa1.as<int32_t>(), d_aas.as<int32_t>(), d_aan.as<int32_t>());
         LAUNCH_CHECK();
     }
-    PGX_HIP(hipMemsetAsync(d_visits.p, 0, 8, st));
-
-    phase("alloc + upload + encode (enq)");
+    phase("alloc + sort + layout + encode (enq)");
     // ---- word lists: size classes are contiguous because the order is by length ----------
     {
         const int wl = P->word_len;
-        auto first_with_words_le = [&](uint32_t cap) {  // first k whose word count fits `cap`
-            return (uint32_t)(std::partition_point(h_len.begin(), h_len.begin() + n,
-                                                   [&](uint32_t L) { return L - wl + 1 > cap; }) - h_len.begin());
-        };
+        auto first_with_words_le = [&](uint32_t cap) { return pgxc::first_with_words_le(run_pos, max_len, cap, wl); };
         const uint32_t k32 = first_with_words_le(32768), k8 = first_with_words_le(8192),
                        k2 = first_with_words_le(2048), k1k = first_with_words_le(1023), k5 = first_with_words_le(512);
         int rc;
@@ -2798,6 +2986,35 @@ static int cluster_greedy_impl(pgx_ctx *ctx, const uint8_t *d_residues, const ui
     PGX_HIP(hipMemcpyAsync(h_wcnt.data(), d_wcnt.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
 
     phase("word lists (enqueue)");
+    // ---- the host's copy of the layout, the windows' geometry (behind the enqueued work) ---
+    fill_host_layout();
+    phase("host lengths + offsets");
+    uint64_t max_window_words = 0;
+    uint32_t max_chunks = 1;   // the tag records are only as long as some window has chunks
+    {
+        Chunks C;
+        size_t nf = 0;
+        for (uint32_t b0 = 0, nbw; b0 < n; b0 += nbw) {
+            while (nf < flush_at.size() && flush_at[nf] <= b0) ++nf;
+            nbw = form_window(b0, C, nf < flush_at.size() ? flush_at[nf] : n);
+            max_window_words = std::max<uint64_t>(max_window_words, h_off[b0 + nbw] - h_off[b0]);
+            max_chunks = std::max(max_chunks, C.n);
+        }
+        if (!flush_at.empty())   // (the sweeps' windows start anywhere: no window holds more than the window_cap longest sequences)
+            max_window_words = std::max<uint64_t>(max_window_words, h_off[std::min(n, window_cap)]);
+    }
+    // The chunk volume adapts (cur_frac below), so later windows are not the ones of this scan: bound a window's words
+    // independently of the partition -- no more than the window_cap longest sequences, no more than kMaxChunks
+    // chunks of the largest volume (a chunk closes before it would exceed that, or holds one sequence).
+    if (chunking && flush_at.empty())
+        max_window_words = std::max<uint64_t>(max_window_words,
+            std::min<uint64_t>(h_off[std::min(n, window_cap)], (uint64_t)kMaxChunks * std::max<uint64_t>(chunk_words, max_len)));
+    PGX_REQUIRE(max_window_words < 0xFFFFFFF0ull, "window too large");
+    PGX_HIP(d_touched.alloc((max_window_words + 16) * sizeof(Deferred)));   // entries set aside by an append round
+    if (chunking && n > window_cap / 2) max_chunks = kMaxChunks;   // (smaller chunks later may need all of them)
+    uint32_t tag_stride = 1;   // first-open tags: one record of tag_stride >= max_chunks words per code
+    while (tag_stride < max_chunks) tag_stride *= 2;
+    PGX_HIP(d_first.alloc((size_t)tag_stride * n_codes * 4 + 16));
     // ---- windows --------------------------------------------------------------------------
     std::vector<uint32_t> rep_seq;            // representative index -> sorted sequence index
     HostVec<int32_t> cluster_of(ctx, 9, n, -1);   // sorted sequence index -> cluster
