@@ -47,6 +47,16 @@ def test_filter_cutoffs_never_fall_below_the_analytic_bound():
         cluster.filter_cutoffs(0.8, 5, tolerance=3)
 
 
+def test_band_width_is_accepted_from_1_to_64_only():
+    for b in (1, 20, 64):
+        for alphabet in ('aa', 'nt'):
+            assert cluster.params_from_cdhit_args({'-n': 5, '-c': 0.8, '-b': b}, alphabet).band_width == b
+    for b in (0, 65, -1, 100):
+        for alphabet in ('aa', 'nt'):
+            with pytest.raises(ValueError, match='-b %d out of range' % b):
+                cluster.params_from_cdhit_args({'-n': 5, '-c': 0.8, '-b': b}, alphabet)
+
+
 @pytest.mark.parametrize('bad', [{'-c': 0.3}, {'-n': 6}, {'-n': 1}, {'-c': 0.8, '-l': 2}, {'-c': 0.8, '-G': 0},
                                  {'-c': 0.8, '-d': 20}, {'-c': 0.8, '-sc': 1}, {'-c': 0.8, '-M': 800},
                                  {'-c': 0.8, '-M': 16000}])

@@ -29,7 +29,7 @@ def test_matches_oracle_on_synthetic_sets(name, gpu_ctx):
 
 
 @pytest.mark.parametrize('args', [{'-c': 0.9}, {'-c': 0.7, '-n': 4}, {'-c': 0.97}, {'-c': 0.8, '-n': 3},
-                                  {'-c': 0.8, '-b': 5}, {'-c': 0.8, '-l': 30}])
+                                  {'-c': 0.8, '-b': 5}, {'-c': 0.8, '-l': 30}, {'-b': 1}, {'-b': 64}])
 def test_matches_oracle_for_other_thresholds(args, gpu_ctx):
     res, off, _ = synth.protein_set('tiny').nr_arrays()
     p = params(**args)
