@@ -559,6 +559,29 @@ int pgx_allele_runs_dev(pgx_ctx *ctx, const uint64_t *d_allele_bits, uint32_t n_
                         uint32_t *d_diff_per_run, uint64_t *d_total, int32_t *d_best_allele, uint32_t *d_best_count,
                         void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* Exact search for fixed-length keys in a text (reference pangenome.py:1573-1647 validate_proximal_table_direct, which slides a
+ * window over every contig): text is text_bytes raw bytes, keys n_keys x window raw bytes, found [n_keys] uint8:
+ *   found[k] = 1 iff the window bytes of key k equal text[i .. i + window) for some 0 <= i <= text_bytes - window, else 0.
+ * Bytes are compared as bytes (no case folding, no alphabet, values >= 0x80 allowed); equal keys given twice are both
+ * flagged. Hashes only decide where to look -- a key is flagged after its bytes have been compared -- so the result is exact;
+ * PGX_SCAN_NARROW_HASH (a test seam) keeps only the low 3 bits of every hash: same results, every probe collides.
+ * window outside 1..1024, text_bytes >= 2^32, n_keys >= 2^24 or unknown flags fail with PGX_ERR_INVALID before anything is
+ * launched or written. n_keys = 0 does nothing; a text shorter than window (text_bytes = 0 included) zeroes found.
+ *   pgx_window_scan      HOST pointers; the device buffers stay in the context between calls
+ *   pgx_window_scan_dev  d_text, d_keys, d_found and the workspace (pgx_window_scan_workspace_bytes(), 16-byte aligned; 0 for
+ *                        sizes that are refused) are the caller's DEVICE pointers. Plain launches on `stream`, which is
+ *                        synchronised once at the end; text and keys are not written, nothing outside found and the
+ *                        workspace is.
+ * pgx_window_scan_tile(): the text positions one workgroup takes at a time. */
+#define PGX_SCAN_NARROW_HASH 1u   /* keep only the low 3 bits of every hash: same results, every probe collides */
+uint32_t pgx_window_scan_tile(void);
+size_t pgx_window_scan_workspace_bytes(uint64_t text_bytes, uint32_t n_keys, uint32_t window);
+int pgx_window_scan(pgx_ctx *ctx, const uint8_t *text, uint64_t text_bytes, const uint8_t *keys, uint32_t n_keys,
+                    uint32_t window, uint32_t flags, uint8_t *out_found);
+int pgx_window_scan_dev(pgx_ctx *ctx, const uint8_t *d_text, uint64_t text_bytes, const uint8_t *d_keys, uint32_t n_keys,
+                        uint32_t window, uint32_t flags, uint8_t *d_found, void *d_workspace, size_t workspace_bytes,
+                        void *stream);
+
 /* feature names (pangenome.py:1944-1969) as fixed-width zero-padded ASCII records (numpy 'S<width>'):
  * <prefix><cluster>[<variant><member>]; variant NULL = gene names */
 int pgx_format_labels(const char *prefix, const char *variant, const int32_t *cluster, const int32_t *member,

@@ -159,6 +159,10 @@ SIGNATURES = {
                                   _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'pgx_allele_runs_dev': (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, _P, _P, _P, _P, _P,
                                       _P, _P, _P, C.c_size_t, _P]),
+    'pgx_window_scan_tile': (C.c_uint32, []),
+    'pgx_window_scan_workspace_bytes': (C.c_size_t, [C.c_uint64, C.c_uint32, C.c_uint32]),
+    'pgx_window_scan': (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P]),
+    'pgx_window_scan_dev': (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, C.c_size_t, _P]),
     'pgx_cluster_greedy': (C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(ClusterParams), _P, _P, _P, _P,
                                      C.POINTER(C.c_uint32), C.POINTER(ClusterStats)]),
     'pgx_cluster_window_cap': (C.c_uint32, [C.POINTER(ClusterParams)]),
@@ -714,6 +718,26 @@ class Context(object):
         check(lib().pgx_allele_runs_dev(self._h, d_allele_bits, int(n_alleles), d_gene_bits, int(n_genes), int(n_genomes),
                                         d_run_start, int(n_runs), d_gene_of_run, d_derived, d_diff, d_diff_per_genome,
                                         d_diff_per_run, d_total, d_best_allele, d_best_count, d_ws, int(ws_bytes), stream))
+
+    # -- fixed-length keys in a text (pangenome.validate_proximal_table_direct) ---------------------------------------------
+    def window_scan(self, text, keys, flags=0):
+        """found uint8 [n_keys]: 1 where the row of `keys` (uint8 [n_keys, window]) occurs anywhere in `text` (bytes or a
+        1-D uint8 array), compared byte by byte (pgx.h: pgx_window_scan). flags: SCAN_NARROW_HASH, the test seam."""
+        if isinstance(text, (bytes, bytearray, memoryview)):
+            text = np.frombuffer(text, dtype=np.uint8)
+        text = np.ascontiguousarray(text, dtype=np.uint8)
+        keys = np.ascontiguousarray(keys, dtype=np.uint8)
+        if text.ndim != 1 or keys.ndim != 2:
+            raise ValueError('text must be 1-D and keys [n_keys, window]')
+        found = np.zeros(keys.shape[0], dtype=np.uint8)
+        check(lib().pgx_window_scan(self._h, _ptr(text), text.size, _ptr(keys), keys.shape[0], keys.shape[1], int(flags),
+                                    _ptr(found)))
+        return found
+
+    def window_scan_dev(self, d_text, text_bytes, d_keys, n_keys, window, d_found, d_ws, ws_bytes, flags=0, stream=0):
+        """The same on device memory (raw device addresses; synchronises `stream`, see pgx.h)."""
+        check(lib().pgx_window_scan_dev(self._h, d_text, int(text_bytes), d_keys, int(n_keys), int(window), int(flags), d_found,
+                                        d_ws, int(ws_bytes), stream))
 
     def pan_core(self, bits, n_genes, perms):
         perms = np.ascontiguousarray(perms, dtype=np.int32)

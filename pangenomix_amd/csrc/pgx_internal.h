@@ -157,7 +157,7 @@ struct DevBuf {
 
 // Workspace slot of the pipeline's resident bitmap (pancore.hip), read in place by bernoulli.hip. Slots in use:
 // pancore 80-94, heaps 96-98, bernoulli 100-107, betabinom 110-116 (host staging slots 110-112), fcd 120-129 (host scratch slot 120),
-// assoc 130-141 (host scratch slot 130), runs 150-167 (host scratch slot 150).
+// assoc 130-141 (host scratch slot 130), runs 150-167 (host scratch slot 150), scan 170-173.
 constexpr int PGX_SLOT_RESIDENT = 90;
 
 static inline uint32_t ceil_div_u32(uint32_t a, uint32_t b) { return (a + b - 1) / b; }

@@ -13,6 +13,7 @@ Drop-in mirror of the reference entry points in pangenomix/pangenome.py
      LightSparseDataFrame.to_npz   .npz + .labels.txt               (H5)
      extract_noncoding             GFF+FNA -> feature FASTA         (H6)
   build_upstream/downstream/proximal_pangenome   5'/3' UTR pangenomes
+  validate_upstream/downstream/proximal_table_direct   the recorded UTRs searched in the genomes -> HIP (csrc/scan.hip)
 
 Same names, positional order, defaults, intermediate files and return values.
 The only behavioural differences are deliberate: a failing
@@ -1194,3 +1195,171 @@ def extract_dominant_alleles(allele_table, allele_faa_file, dominant_out, ctx=No
                 f_dom.write(line)
     print(alleles_written)
     return df_dominant
+
+
+# ---------------------------------------------------------------------------
+# UTR tables against the genomes (reference :1549-1647): the table's sequences are searched in every contig and its
+# reverse complement -- one window scan per genome on the device (csrc/scan.hip)
+# ---------------------------------------------------------------------------
+_COMPLEMENT_BYTES = ''.join(sorted(_COMPLEMENT_KEYS)).encode('ascii')
+SCAN_MAX_WINDOW = 1024             # csrc/scan.hip
+
+
+def _check_contig(contig):
+    """The contig as bytes; KeyError(first character outside the complement table), which is what the reference's
+    reverse_complement(contig) raises (:1621)."""
+    try:
+        raw = contig.encode('ascii')
+    except UnicodeEncodeError:
+        raw = None
+    if raw is None or raw.translate(None, _COMPLEMENT_BYTES):
+        reverse_complement(contig)          # raises KeyError(base)
+    return raw
+
+
+def _scan_keys(sequences, window):
+    """The keys of one window scan: (keys uint8 [n_keys, window], forward, reverse) for `sequences`, distinct strings of
+    length `window`. forward[i] / reverse[i] are the rows of sequence i and of its reverse complement, -1 for none: a
+    sequence that is not ASCII has no forward key (no checked contig holds such a character), one with a character outside
+    the complement table no reverse key (it cannot occur in a reverse complement). Equal byte strings share one row
+    (palindromes; P == rc(Q)). A key holding the byte 0x00, which joins the contigs, raises ValueError."""
+    row_of = {}
+    forward = np.full(len(sequences), -1, dtype=np.int64)
+    reverse = np.full(len(sequences), -1, dtype=np.int64)
+    for i, seq in enumerate(sequences):
+        try:
+            raw = seq.encode('ascii')
+        except UnicodeEncodeError:
+            continue
+        if b'\x00' in raw:
+            raise ValueError('a table sequence holds the byte 0x00')
+        forward[i] = row_of.setdefault(raw, len(row_of))
+        if not raw.translate(None, _COMPLEMENT_BYTES):
+            reverse[i] = row_of.setdefault(seq.translate(_COMPLEMENT)[::-1].encode('ascii'), len(row_of))
+    keys = np.frombuffer(b''.join(row_of), dtype=np.uint8).reshape(len(row_of), window)
+    return keys, forward, reverse
+
+
+def _short_sequence_found(seq, contigs):
+    """The reference's slices at a contig's end are shorter than the window (contig[i:i+window] near len(contig)), so a
+    sequence SHORTER than the window matches iff it is a suffix of a contig or of a contig's reverse complement.
+    `contigs` have passed _check_contig."""
+    m = len(seq)
+    for contig in contigs:
+        if len(contig) >= m and (contig.endswith(seq) or contig[:m].translate(_COMPLEMENT)[::-1] == seq):
+            return True
+    return False
+
+
+def _genome_missing(sequences, contigs, window, scan):
+    """found (list of bool) for the distinct table sequences of one genome. scan(text, keys) -> found per key."""
+    raws = [_check_contig(c) for c in contigs]
+    found = [False] * len(sequences)
+    full = [i for i, seq in enumerate(sequences) if len(seq) == window]
+    for i, seq in enumerate(sequences):
+        if len(seq) < window:
+            found[i] = _short_sequence_found(seq, contigs)
+    if full and raws:
+        keys, forward, reverse = _scan_keys([sequences[i] for i in full], window)
+        if keys.shape[0]:
+            hit = np.concatenate([np.asarray(scan(b'\x00'.join(raws), keys), dtype=bool), [False]])   # (-1: the last one)
+            for i, ok in zip(full, (hit[forward] | hit[reverse]).tolist()):
+                found[i] = ok
+    return found
+
+
+def validate_proximal_table_direct(df_prox, genome_fna_paths, nr_prox_fna, limits, side, log_group=1, ctx=None):
+    """Partial validation of a proximal x genome table (reference :1573-1647): every sequence the table records for a genome
+    must occur in one of the genome's contigs or in a contig's reverse complement; then the start (upstream) or stop
+    (downstream) codons among the non-redundant sequences are counted. It does not check WHERE a sequence occurs.
+    The printed output is the reference's; the return value is the number of `Missing` lines (the reference returns None).
+
+    df_prox: LightSparseDataFrame (what build_upstream_pangenome returns; its stored entries, which must all be 1), pandas
+    frame (every cell that is not NaN, :1612) or a path. genome_fna_paths are taken in the given order; a genome that is no
+    column raises KeyError(genome), a recorded row that is not in nr_prox_fna KeyError(label), a contig character outside the
+    complement table KeyError(character) -- each where the reference raises it, after that genome's `Evaluating` line.
+    Rows of a genome that share a sequence are reported once, at the place of the first and under the name of the last.
+    The reference compares the slices contig[i:i+window], window = limits[1] - limits[0], which are shorter at a contig's
+    end ("does not yet support non-fixed length UTRs"): a sequence of exactly `window` characters matches wherever it
+    occurs -- the device's work, one exact multi-pattern scan per genome (csrc/scan.hip) over the contigs joined by a 0x00
+    byte, the reverse strand being searched through the reverse complements of the keys; a shorter sequence matches only as
+    the suffix of a contig or of its reverse complement; a longer one never. window must be 1..1024 (ValueError). The next
+    genome's FNA is parsed on a host thread while the device scans. There is no CPU fallback."""
+    import collections
+    from concurrent.futures import ThreadPoolExecutor
+    who = 'validate_proximal_table_direct'
+    rows, cols, labels, columns = _table_cells(_load_table(df_prox), who, notna=True)
+    window = limits[1] - limits[0]
+    if not 1 <= window <= SCAN_MAX_WINDOW:
+        raise ValueError(who + ' needs 1 <= limits[1] - limits[0] <= %d' % SCAN_MAX_WINDOW)
+    order = np.lexsort((rows, cols))
+    rows, cols = rows[order], cols[order]
+    col_start = np.searchsorted(cols, np.arange(columns.size + 1))
+    column_of = {}
+    for j, label in enumerate(columns.tolist()):
+        column_of.setdefault(label, j)
+    labels = labels.tolist()
+
+    print('Loading', side, 'sequences...')
+    nr_prox = load_sequences_from_fasta(nr_prox_fna)
+
+    def scan(text, keys):
+        nonlocal ctx
+        if ctx is None:
+            from . import _native
+            ctx = _native.default_context()
+        return ctx.window_scan(text, keys)
+
+    missing = 0
+    genome_fna_paths = list(genome_fna_paths)
+    with ThreadPoolExecutor(max_workers=1) as pool:
+        ahead = pool.submit(load_sequences_from_fasta, genome_fna_paths[0]) if genome_fna_paths else None
+        for g, genome_fna in enumerate(genome_fna_paths):
+            genome_contigs = ahead.result()
+            ahead = pool.submit(load_sequences_from_fasta, genome_fna_paths[g + 1]) if g + 1 < len(genome_fna_paths) else None
+            genome = __get_genome_from_filename__(genome_fna)
+            if (g + 1) % log_group == 0:
+                print(g + 1, 'Evaluating', genome, genome_fna)
+            if genome not in column_of:
+                raise KeyError(genome)
+            j = column_of[genome]
+            table_prox_seqs = {}                       # sequence -> name: first row's place, last row's name (:1613)
+            for r in rows[col_start[j]:col_start[j + 1]].tolist():
+                table_prox_seqs[nr_prox[labels[r]]] = labels[r]
+            sequences = list(table_prox_seqs)
+            found = _genome_missing(sequences, list(genome_contigs.values()), window, scan)
+            for seq, ok in zip(sequences, found):
+                if not ok:
+                    print('\tMissing', table_prox_seqs[seq], 'from', genome)
+                    missing += 1
+
+    if limits[1] >= 3 and side == 'upstream':
+        print('Computing start codon distribution...')
+        if limits[1] == 3:
+            get_start = lambda x: x[-3:]
+        else:
+            get_start = lambda x: x[-limits[1]:-limits[1] + 3]
+        print(collections.Counter(map(get_start, nr_prox.values())))
+    elif limits[0] <= -3 and side == 'downstream':
+        print('Computing stop codon distribution...')
+        if limits[0] == -3:
+            get_stop = lambda x: x[:3]
+        else:
+            get_stop = lambda x: x[-limits[0] - 3:-limits[0]]
+        print(collections.Counter(map(get_stop, nr_prox.values())))
+    return missing
+
+
+def validate_upstream_table_direct(df_upstream, genome_fna_paths, nr_upstream_fna, limits=(-50, 3), log_group=1, ctx=None):
+    """validate_proximal_table_direct(..., side='upstream') (reference :1549-1558, which calls the undefined name
+    validate_proximal_table and so always raises NameError; here the wrapper calls the function that exists). Returns the
+    number of missing sequences."""
+    return validate_proximal_table_direct(df_upstream, genome_fna_paths, nr_upstream_fna, limits, 'upstream', log_group, ctx)
+
+
+def validate_downstream_table_direct(df_downstream, genome_fna_paths, nr_downstream_fna, limits=(-3, 50), log_group=1,
+                                     ctx=None):
+    """validate_proximal_table_direct(..., side='downstream') (reference :1561-1570, with the same NameError as the upstream
+    wrapper; fixed in the same way). Returns the number of missing sequences."""
+    return validate_proximal_table_direct(df_downstream, genome_fna_paths, nr_downstream_fna, limits, 'downstream', log_group,
+                                          ctx)
