@@ -13,6 +13,9 @@
  *                                       pgx_pan_core*
  *   pangenome_analysis.py:101-166       compute_bernoulli_grid_core_genome(): the dense
  *                                       numpy likelihood and gradient -> pgx_bernoulli_*
+ *   pangenome_analysis.py:169-242       compute_bernoulli_grid_core_genome_cd(): one scipy
+ *                                       brentq call per gene and genome and sweep
+ *                                       -> pgx_bernoulli_cd*
  *   pangenome_analysis.py:457-492       ks_montecarlo_bbn() / draw_bbn(): np.random.choice
  *                                       and the per-iteration eCDF loop -> pgx_bbn_*
  *   fcd.py:15-138, :199-219             formal_concept_decomposition() / compute_concept_coverage(): the dense
@@ -31,7 +34,8 @@
  *   - *_dev variants take DEVICE pointers and a hipStream_t (as void*); they only
  *     enqueue work on that stream (graph-capturable: no allocation, no sync) and are
  *     what bench.py times with inputs resident in HBM. The plain variants take HOST
- *     pointers and do the copies themselves.
+ *     pointers and do the copies themselves. (One exception: pgx_bernoulli_cd_dev
+ *     synchronises its stream once, at its end; see there.)
  *   - there is no CPU fallback: without a usable GPU every compute entry point fails
  *     with PGX_ERR_NO_DEVICE.
  */
@@ -409,6 +413,46 @@ int pgx_bernoulli_load(pgx_ctx *ctx, const int32_t *rows, const int32_t *genomes
 int pgx_bernoulli_load_resident(pgx_ctx *ctx, uint64_t token, const int32_t *row_map, uint32_t n_genes,
                                 uint32_t n_genomes);
 int pgx_bernoulli_eval(pgx_ctx *ctx, const double *pq, uint32_t flags, double *out);
+
+/* Coordinate descent on that likelihood (compute_bernoulli_grid_core_genome_cd, reference pangenome_analysis.py:169-242 and
+ * :251-292), the whole loop on the device. From P = init_p (n_genes values inside [lo, hi]) and Q = init_q everywhere, each
+ * of the n_iterations iterations solves, for every gene i with Q fixed,
+ *   f(p) = rowsum_i / p - sum_{j absent} q_j / (1 - p q_j) = 0        in [lo, hi]
+ * then the same for every genome j with the new P, then takes LL. Inside a sweep no solve depends on another. The rule
+ * around a solve: f is taken at lo and at hi; when f(lo) f(hi) >= 0 the result is lo if |last - lo| < |last - hi| and hi
+ * otherwise (last: the coordinate's previous value) -- which is also where a row present everywhere or nowhere goes --
+ * else the root by Brent's method, stopped when half the bracket is below (2e-12 + 4 x 2^-52 |x|) / 2 or f(x) == 0: the
+ * result lies within 2e-12 + 4 x 2^-52 |x| of a sign change of the computed f. A solve that has not stopped after 100
+ * steps fails the call with PGX_ERR_INTERNAL (the outputs are then unspecified).
+ * flags = PGX_BERNOULLI_CD_LOGS: the solver's variables are lp = log p and lq = log q between log lo and log hi,
+ *   f(lp) = rowsum_i exp(-lp) - sum_{j absent} exp(lq_j) / (-expm1(lp + lq_j)),
+ *   LL    = sum X (lp + lq) + (1 - X) log(-expm1(lp + lq)).
+ * fp64 without contraction or fast division; p q, 1 - p q and each quotient are rounded once each. Deterministic: the
+ * same inputs give the same bits on every call. LL as pgx_bernoulli_eval gives it (its accuracy rule; the log flavour's own
+ * sum under the same rule).
+ * out_table: float64 [1 + n_genes + n_genomes][n_iterations + 1], row-major: row 0 = LL, rows 1.. = P then Q, column 0 =
+ * the start point, column k = after iteration k; in the log flavour exp of the solver's variables. out_solver_table (may
+ * be NULL): the same shape with the solver's own variables (lp, lq in the log flavour, otherwise equal to out_table).
+ * Refused with PGX_ERR_INVALID before anything is launched: n_genes = 0 or n_genomes = 0, unknown flags, not 0 < lo < hi,
+ * init_q <= 0, hi x max(hi, init_q) >= 1, a bound or init_q that is not finite, more than 2^20 iterations, and (host
+ * entry) an init_p outside [lo, hi] -- so that every 1 - p q the call forms is a positive normal number. n_iterations = 0
+ * is valid: one column.
+ *   pgx_bernoulli_cd        on the table loaded by pgx_bernoulli_load / pgx_bernoulli_load_resident; HOST pointers
+ *   pgx_bernoulli_cd_dev    d_bits: the table in the bitmap layout (pad bits beyond n_genes are ignored); d_init_p (the
+ *                           caller keeps it inside [lo, hi]), the result tables and a workspace of
+ *                           pgx_bernoulli_cd_workspace_bytes() are DEVICE pointers; plain launches on `stream`, no
+ *                           allocation, ONE synchronisation of `stream` at the end (the count of failed solves is read);
+ *                           nothing but the results and the workspace is written
+ *   pgx_bernoulli_cd_stats  of the context's last call: {evaluations of f, most evaluations in one solve, solves not
+ *                           converged, solves} (the two evaluations at the bounds included) */
+#define PGX_BERNOULLI_CD_LOGS 1u
+size_t pgx_bernoulli_cd_workspace_bytes(uint32_t n_genes, uint32_t n_genomes);
+int pgx_bernoulli_cd_dev(pgx_ctx *ctx, const uint64_t *d_bits, uint32_t n_genes, uint32_t n_genomes, const double *d_init_p,
+                         double init_q, double lo, double hi, uint32_t n_iterations, uint32_t flags, double *d_out_table,
+                         double *d_out_solver_table, void *d_workspace, size_t workspace_bytes, void *stream);
+int pgx_bernoulli_cd(pgx_ctx *ctx, const double *init_p, double init_q, double lo, double hi, uint32_t n_iterations,
+                     uint32_t flags, double *out_table, double *out_solver_table);
+int pgx_bernoulli_cd_stats(pgx_ctx *ctx, uint64_t *out_stats);
 
 /* Monte-Carlo Kolmogorov-Smirnov test of a beta-binomial fit (ks_montecarlo_bbn / draw_bbn, reference
  * pangenome_analysis.py:457-492). A draw is np.random.choice(arange(L), p=probs) of the legacy generator:

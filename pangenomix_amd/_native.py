@@ -68,6 +68,7 @@ class FcdInfo(C.Structure):
 
 
 FCD_OVERLAP, FCD_DIM_BALANCE = 1, 2    # PGX_FCD_OVERLAP, PGX_FCD_DIM_BALANCE
+BERNOULLI_CD_LOGS = 1                  # PGX_BERNOULLI_CD_LOGS
 ASSOC_BLOCKS, ASSOC_DROP_EMPTY = 1, 2  # PGX_ASSOC_BLOCKS, PGX_ASSOC_DROP_EMPTY
 
 
@@ -132,6 +133,11 @@ SIGNATURES = {
     'pgx_bernoulli_load': (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
     'pgx_bernoulli_load_resident': (C.c_int, [_P, C.c_uint64, _P, C.c_uint32, C.c_uint32]),
     'pgx_bernoulli_eval': (C.c_int, [_P, _P, C.c_uint32, _P]),
+    'pgx_bernoulli_cd_workspace_bytes': (C.c_size_t, [C.c_uint32, C.c_uint32]),
+    'pgx_bernoulli_cd_dev': (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, C.c_double, C.c_double, C.c_double, C.c_uint32,
+                                       C.c_uint32, _P, _P, _P, C.c_size_t, _P]),
+    'pgx_bernoulli_cd': (C.c_int, [_P, _P, C.c_double, C.c_double, C.c_double, C.c_uint32, C.c_uint32, _P, _P]),
+    'pgx_bernoulli_cd_stats': (C.c_int, [_P, _P]),
     'pgx_bbn_workspace_bytes': (C.c_size_t, [C.c_uint32, C.c_uint32]),
     'pgx_bbn_ks_sim_dev': (C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, C.c_size_t, _P]),
     'pgx_bbn_ks_sim': (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, C.POINTER(C.c_int32),
@@ -382,6 +388,14 @@ class Context(object):
         check(lib().pgx_bernoulli_eval_dev(self._h, d_bits, int(n_genes), int(n_genomes), d_pq, int(flags), d_out, d_ws,
                                            int(ws_bytes), stream))
 
+    def bernoulli_cd_dev(self, d_bits, n_genes, n_genomes, d_init_p, init_q, lo, hi, n_iterations, d_table, d_solver,
+                         d_ws, ws_bytes, flags=0, stream=0):
+        """d_table, d_solver (or None): float64 [1 + n_genes + n_genomes, n_iterations + 1]; one synchronisation of
+        `stream` at the end."""
+        check(lib().pgx_bernoulli_cd_dev(self._h, d_bits, int(n_genes), int(n_genomes), d_init_p, float(init_q), float(lo),
+                                         float(hi), int(n_iterations), int(flags), d_table, d_solver, d_ws, int(ws_bytes),
+                                         stream))
+
     # -- K3 ----------------------------------------------------------------
     def presence_bitmap(self, rows, genomes, n_rows, n_genomes, return_duplicates=False):
         rows, genomes = _coo_args(rows, genomes)
@@ -502,6 +516,34 @@ class Context(object):
         out = np.empty(pq.size + 1, dtype=np.float64)
         check(lib().pgx_bernoulli_eval(self._h, _ptr(pq), 1 if exact else 0, _ptr(out)))
         return out
+
+    def bernoulli_cd(self, init_p, init_q, lo, hi, n_iterations, use_logs=False, solver_table=False):
+        """Coordinate descent on the loaded table (pgx.h: pgx_bernoulli_cd): the float64 table
+        [1 + n_genes + n_genomes, n_iterations + 1] (row 0 = LL, column 0 = the start point), and with solver_table=True
+        also the same table in the solver's own variables (logs when use_logs). init_p: n_genes values inside [lo, hi].
+        A solve that does not converge raises PgxError (a RuntimeError)."""
+        shape = getattr(self, '_bern_shape', None)
+        if shape is None:
+            raise PgxError('no table loaded (bernoulli_load / bernoulli_load_resident)')
+        init_p = np.ascontiguousarray(init_p, dtype=np.float64)
+        if init_p.shape != (shape[0],):
+            raise ValueError('init_p must hold n_genes values')
+        n_iterations = int(n_iterations)
+        if n_iterations < 0:
+            raise ValueError('n_iterations must not be negative')
+        table = np.empty((1 + shape[0] + shape[1], n_iterations + 1), dtype=np.float64)
+        solver = np.empty_like(table) if solver_table else None
+        check(lib().pgx_bernoulli_cd(self._h, _ptr(init_p), float(init_q), float(lo), float(hi), n_iterations,
+                                     BERNOULLI_CD_LOGS if use_logs else 0, _ptr(table), _ptr(solver)))
+        return (table, solver) if solver_table else table
+
+    def bernoulli_cd_stats(self):
+        """Of the last bernoulli_cd / bernoulli_cd_dev: evaluations of f, most evaluations in one solve, solves that
+        did not converge, solves."""
+        out = np.zeros(4, dtype=np.uint64)
+        check(lib().pgx_bernoulli_cd_stats(self._h, _ptr(out)))
+        return {'evaluations': int(out[0]), 'max_evaluations': int(out[1]), 'not_converged': int(out[2]),
+                'solves': int(out[3])}
 
     # -- Monte-Carlo KS test of a beta-binomial fit (ks_montecarlo_bbn / draw_bbn) -------------------------------------
     def bbn_ks_sim(self, draw_cdf, model_cdf, n_samples, iterations, key, pos, chunk_draws=0):

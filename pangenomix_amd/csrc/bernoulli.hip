@@ -266,6 +266,7 @@ __global__ __launch_bounds__(BN_THREADS) void bern_gather_rows_kernel(const unsi
 
 // device buffers of the host-pointer entry points (slots after pan/core's and the Heaps fit's)
 enum { BN_SLOT_BITS = 100, BN_SLOT_ROWS, BN_SLOT_GENOMES, BN_SLOT_CNT, BN_SLOT_MAP, BN_SLOT_PQ, BN_SLOT_OUT, BN_SLOT_WS };
+static_assert(BN_SLOT_BITS == PGX_SLOT_BERN_BITS, "bernoulli_cd.hip reads the loaded table from this slot");
 struct BnBuf : DevBuf {
     BnBuf(pgx_ctx *c, int s) { ctx = c; slot = s; }
 };

@@ -47,6 +47,8 @@ struct pgx_ctx {
     // the table loaded for Bernoulli likelihood evaluations (pgx_bernoulli_load*): its shape; the bitmap is a workspace slot
     uint32_t bern_genes = 0, bern_genomes = 0;
     bool bern_loaded = false;
+    // of the last coordinate descent on it (pgx_bernoulli_cd*): evaluations of f, most of one solve, solves not converged, solves
+    uint64_t bern_cd_stats[4] = {0, 0, 0, 0};
     // the concepts of the last formal concept decomposition (pgx_fcd*), kept for pgx_fcd_fetch: row / column indices of
     // all concepts end to end, the offsets of each concept in them (n + 1 entries), the ones left uncovered after each
     std::vector<int32_t> fcd_rows, fcd_cols;
@@ -157,8 +159,10 @@ struct DevBuf {
 
 // Workspace slot of the pipeline's resident bitmap (pancore.hip), read in place by bernoulli.hip. Slots in use:
 // pancore 80-94, heaps 96-98, bernoulli 100-107, betabinom 110-116 (host staging slots 110-112), fcd 120-129 (host scratch slot 120),
-// assoc 130-141 (host scratch slot 130), runs 150-167 (host scratch slot 150), scan 170-173.
+// assoc 130-141 (host scratch slot 130), runs 150-167 (host scratch slot 150), scan 170-173, bernoulli_cd 180-183.
 constexpr int PGX_SLOT_RESIDENT = 90;
+// Workspace slot of the table loaded by pgx_bernoulli_load* (bernoulli.hip), read in place by bernoulli_cd.hip.
+constexpr int PGX_SLOT_BERN_BITS = 100;
 
 static inline uint32_t ceil_div_u32(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
 
