@@ -626,6 +626,57 @@ int pgx_window_scan_dev(pgx_ctx *ctx, const uint8_t *d_text, uint64_t text_bytes
                         uint32_t window, uint32_t flags, uint8_t *d_found, void *d_workspace, size_t workspace_bytes,
                         void *stream);
 
+/* Exact look-up of whole byte strings in a set of byte strings (reference pangenome.py:1418-1546 validate_table_against_fasta,
+ * which does one SHA-256 and one dict look-up per FASTA record). String i of a blob is the bytes [offsets[i], offsets[i + 1]):
+ * offsets holds n + 1 entries that never decrease, offsets[0] may be non-zero, the blob is the bytes [0, offsets[n]) and may
+ * start at any address; nothing outside it is read. The empty string is a legal key and a legal query. Bytes are compared
+ * as bytes (values >= 0x80 allowed); two strings are equal iff they have the same length and the same bytes.
+ *   first[k] = the smallest index of a key equal to key k (k itself for the first of its kind)
+ *   last[q]  = the largest index of a key equal to query q, -1 for none
+ * Both are a minimum / maximum over a set: the same input gives the same output on every call. Hashes only decide where to
+ * look -- an index is reported after lengths and bytes have been compared -- so the result is exact (the reference compares
+ * SHA-256 digests; the two agree unless SHA-256 collides). PGX_DICT_NARROW_HASH (a test seam) keeps only the low 3 bits of
+ * every hash: same results, every probe collides, the look-up is then quadratic in the number of keys.
+ * n_keys >= 2^24, n_queries >= 2^31, a blob of 2^32 bytes or more or decreasing offsets (host entries), unknown flags and
+ * too small a workspace fail with PGX_ERR_INVALID before anything is launched or written. n_keys = 0 gives every query -1; n_queries = 0 does nothing.
+ *   pgx_dict_load       HOST pointers: keeps the keys and their table in the context, replacing an earlier set; out_first
+ *                       [n_keys] may be NULL
+ *   pgx_dict_query      HOST pointers: searches the set loaded last (PGX_ERR_INVALID without one), with the flags it was
+ *                       loaded with; any number of calls per load
+ *   pgx_dict_match_dev  keys, queries, offsets (8-byte aligned), outputs (d_out_first may be NULL) and the workspace
+ *                       (pgx_dict_workspace_bytes(), 16-byte aligned; 0 for sizes that are refused) are the caller's DEVICE
+ *                       pointers. Plain launches on `stream`, which is synchronised once at the end; inputs are not written,
+ *                       nothing outside the outputs and the workspace is. Device offsets are not checked, and the LAST offset is taken
+ *                       as the blob's size: d_keys must hold d_key_offsets[n_keys] bytes and d_queries
+ *                       d_query_offsets[n_queries] bytes. The kernels clamp every string into [0, last offset), so with a
+ *                       last offset inside the caller's allocation nothing outside it is read whatever the other offsets
+ *                       hold (the result for broken offsets is unspecified); a last offset beyond the allocation is the
+ *                       caller's error and is not caught.
+ * pgx_dict_group_bytes(): the bytes of a string the lanes that share it take per step. */
+#define PGX_DICT_NARROW_HASH 1u   /* keep only the low 3 bits of every hash: same results, every probe collides */
+uint32_t pgx_dict_group_bytes(void);
+size_t pgx_dict_workspace_bytes(uint64_t key_bytes, uint32_t n_keys);
+int pgx_dict_load(pgx_ctx *ctx, const uint8_t *keys, const uint64_t *key_offsets, uint32_t n_keys, uint32_t flags,
+                  int32_t *out_first);
+int pgx_dict_query(pgx_ctx *ctx, const uint8_t *queries, const uint64_t *query_offsets, uint32_t n_queries,
+                   int32_t *out_last);
+int pgx_dict_match_dev(pgx_ctx *ctx, const uint8_t *d_keys, const uint64_t *d_key_offsets, uint32_t n_keys,
+                       const uint8_t *d_queries, const uint64_t *d_query_offsets, uint32_t n_queries, uint32_t flags,
+                       int32_t *d_out_first, int32_t *d_out_last, void *d_workspace, size_t workspace_bytes, void *stream);
+
+/* Two sets of rows per genome, compared: A and B are bitmaps in the layout of pgx_presence_bitmap (n_genomes x
+ * pgx_bitmap_stride_words(n_rows) words, row r = bit r & 63 of word r >> 6 of the genome's words);
+ *   a_only[g] = rows of genome g set in A and not in B,   b_only[g] = rows set in B and not in A.
+ * Bits at or beyond n_rows are masked, not trusted. n_rows, n_genomes < 2^31; n_genomes = 0 does nothing.
+ *   pgx_genome_sets_diff      HOST COO coordinates of both sets; a coordinate given twice counts once, one out of range
+ *                             fails with PGX_ERR_INVALID
+ *   pgx_genome_sets_diff_dev  the caller's DEVICE bitmaps and outputs; one launch on `stream`, which is then synchronised */
+int pgx_genome_sets_diff(pgx_ctx *ctx, const int32_t *a_rows, const int32_t *a_genomes, uint64_t n_a, const int32_t *b_rows,
+                         const int32_t *b_genomes, uint64_t n_b, uint32_t n_rows, uint32_t n_genomes, uint32_t *out_a_only,
+                         uint32_t *out_b_only);
+int pgx_genome_sets_diff_dev(pgx_ctx *ctx, const uint64_t *d_a_bits, const uint64_t *d_b_bits, uint32_t n_rows,
+                             uint32_t n_genomes, uint32_t *d_a_only, uint32_t *d_b_only, void *stream);
+
 /* feature names (pangenome.py:1944-1969) as fixed-width zero-padded ASCII records (numpy 'S<width>'):
  * <prefix><cluster>[<variant><member>]; variant NULL = gene names */
 int pgx_format_labels(const char *prefix, const char *variant, const int32_t *cluster, const int32_t *member,

@@ -70,6 +70,7 @@ class FcdInfo(C.Structure):
 FCD_OVERLAP, FCD_DIM_BALANCE = 1, 2    # PGX_FCD_OVERLAP, PGX_FCD_DIM_BALANCE
 BERNOULLI_CD_LOGS = 1                  # PGX_BERNOULLI_CD_LOGS
 ASSOC_BLOCKS, ASSOC_DROP_EMPTY = 1, 2  # PGX_ASSOC_BLOCKS, PGX_ASSOC_DROP_EMPTY
+DICT_NARROW_HASH = 1                   # PGX_DICT_NARROW_HASH
 
 
 # every symbol include/pgx.h declares: (restype, argtypes)
@@ -169,6 +170,13 @@ SIGNATURES = {
     'pgx_window_scan_workspace_bytes': (C.c_size_t, [C.c_uint64, C.c_uint32, C.c_uint32]),
     'pgx_window_scan': (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P]),
     'pgx_window_scan_dev': (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, C.c_size_t, _P]),
+    'pgx_dict_group_bytes': (C.c_uint32, []),
+    'pgx_dict_workspace_bytes': (C.c_size_t, [C.c_uint64, C.c_uint32]),
+    'pgx_dict_load': (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _P]),
+    'pgx_dict_query': (C.c_int, [_P, _P, _P, C.c_uint32, _P]),
+    'pgx_dict_match_dev': (C.c_int, [_P, _P, _P, C.c_uint32, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_size_t, _P]),
+    'pgx_genome_sets_diff': (C.c_int, [_P, _P, _P, C.c_uint64, _P, _P, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P]),
+    'pgx_genome_sets_diff_dev': (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P]),
     'pgx_cluster_greedy': (C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(ClusterParams), _P, _P, _P, _P,
                                      C.POINTER(C.c_uint32), C.POINTER(ClusterStats)]),
     'pgx_cluster_window_cap': (C.c_uint32, [C.POINTER(ClusterParams)]),
@@ -780,6 +788,57 @@ class Context(object):
         """The same on device memory (raw device addresses; synchronises `stream`, see pgx.h)."""
         check(lib().pgx_window_scan_dev(self._h, d_text, int(text_bytes), d_keys, int(n_keys), int(window), int(flags), d_found,
                                         d_ws, int(ws_bytes), stream))
+
+    # -- whole strings in a set of strings (pangenome.validate_table_against_fasta) -----------------------------------------
+    @staticmethod
+    def _string_args(blob, offsets):
+        if isinstance(blob, (bytes, bytearray, memoryview)):
+            blob = np.frombuffer(blob, dtype=np.uint8)
+        blob = np.ascontiguousarray(blob, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if blob.ndim != 1 or offsets.ndim != 1 or offsets.size < 1:
+            raise ValueError('a blob must be 1-D and offsets hold n + 1 entries')
+        if int(offsets[-1]) > blob.size:
+            raise ValueError('offsets run past the end of the blob')
+        return blob, offsets
+
+    def dict_load(self, keys, key_offsets, flags=0, want_first=True):
+        """Loads the keys -- key i is the bytes keys[key_offsets[i]:key_offsets[i + 1]] -- for dict_query, replacing an
+        earlier set. Returns first int32 [n_keys]: the smallest index of a key with key i's bytes (pgx.h: pgx_dict_load), or
+        None if not wanted. flags: DICT_NARROW_HASH, the test seam."""
+        keys, key_offsets = self._string_args(keys, key_offsets)
+        first = np.zeros(key_offsets.size - 1, dtype=np.int32) if want_first else None
+        check(lib().pgx_dict_load(self._h, _ptr(keys), _ptr(key_offsets), key_offsets.size - 1, int(flags), _ptr(first)))
+        return first
+
+    def dict_query(self, queries, query_offsets):
+        """last int32 [n_queries]: the largest index of a loaded key with the query's bytes, -1 for none."""
+        queries, query_offsets = self._string_args(queries, query_offsets)
+        last = np.zeros(query_offsets.size - 1, dtype=np.int32)
+        check(lib().pgx_dict_query(self._h, _ptr(queries), _ptr(query_offsets), query_offsets.size - 1, _ptr(last)))
+        return last
+
+    def dict_match_dev(self, d_keys, d_key_offsets, n_keys, d_queries, d_query_offsets, n_queries, d_out_first, d_out_last,
+                       d_ws, ws_bytes, flags=0, stream=0):
+        """Both on device memory (raw device addresses, None for no first; synchronises `stream`, see pgx.h)."""
+        check(lib().pgx_dict_match_dev(self._h, d_keys, d_key_offsets, int(n_keys), d_queries, d_query_offsets, int(n_queries),
+                                       int(flags), d_out_first, d_out_last, d_ws, int(ws_bytes), stream))
+
+    def genome_sets_diff(self, a_rows, a_genomes, b_rows, b_genomes, n_rows, n_genomes):
+        """(a_only, b_only) uint32 [n_genomes]: per genome the rows of the COO set A that B lacks and the other way round;
+        a coordinate given twice counts once (pgx.h: pgx_genome_sets_diff)."""
+        a_rows, a_genomes = _coo_args(a_rows, a_genomes)
+        b_rows, b_genomes = _coo_args(b_rows, b_genomes)
+        a_only = np.zeros(int(n_genomes), dtype=np.uint32)
+        b_only = np.zeros(int(n_genomes), dtype=np.uint32)
+        check(lib().pgx_genome_sets_diff(self._h, _ptr(a_rows), _ptr(a_genomes), a_rows.size, _ptr(b_rows), _ptr(b_genomes),
+                                         b_rows.size, int(n_rows), int(n_genomes), _ptr(a_only), _ptr(b_only)))
+        return a_only, b_only
+
+    def genome_sets_diff_dev(self, d_a_bits, d_b_bits, n_rows, n_genomes, d_a_only, d_b_only, stream=0):
+        """The same on device bitmaps (raw device addresses; synchronises `stream`, see pgx.h)."""
+        check(lib().pgx_genome_sets_diff_dev(self._h, d_a_bits, d_b_bits, int(n_rows), int(n_genomes), d_a_only, d_b_only,
+                                             stream))
 
     def pan_core(self, bits, n_genes, perms):
         perms = np.ascontiguousarray(perms, dtype=np.int32)

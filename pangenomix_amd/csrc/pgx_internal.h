@@ -49,6 +49,11 @@ struct pgx_ctx {
     bool bern_loaded = false;
     // of the last coordinate descent on it (pgx_bernoulli_cd*): evaluations of f, most of one solve, solves not converged, solves
     uint64_t bern_cd_stats[4] = {0, 0, 0, 0};
+    // the set of keys loaded for exact look-ups (pgx_dict_load): how many, the flags they were hashed with, and the device
+    // pointers of keys, offsets and table (workspace slots only dict.hip uses; valid while dict_loaded)
+    bool dict_loaded = false;
+    uint32_t dict_keys = 0, dict_flags = 0;
+    const void *dict_d_keys = nullptr, *dict_d_offsets = nullptr, *dict_d_table = nullptr;
     // the concepts of the last formal concept decomposition (pgx_fcd*), kept for pgx_fcd_fetch: row / column indices of
     // all concepts end to end, the offsets of each concept in them (n + 1 entries), the ones left uncovered after each
     std::vector<int32_t> fcd_rows, fcd_cols;
@@ -159,7 +164,7 @@ struct DevBuf {
 
 // Workspace slot of the pipeline's resident bitmap (pancore.hip), read in place by bernoulli.hip. Slots in use:
 // pancore 80-94, heaps 96-98, bernoulli 100-107, betabinom 110-116 (host staging slots 110-112), fcd 120-129 (host scratch slot 120),
-// assoc 130-141 (host scratch slot 130), runs 150-167 (host scratch slot 150), scan 170-173, bernoulli_cd 180-183.
+// assoc 130-141 (host scratch slot 130), runs 150-167 (host scratch slot 150), scan 170-173, bernoulli_cd 180-183, dict 190-202.
 constexpr int PGX_SLOT_RESIDENT = 90;
 // Workspace slot of the table loaded by pgx_bernoulli_load* (bernoulli.hip), read in place by bernoulli_cd.hip.
 constexpr int PGX_SLOT_BERN_BITS = 100;

@@ -14,6 +14,8 @@ Drop-in mirror of the reference entry points in pangenomix/pangenome.py
      extract_noncoding             GFF+FNA -> feature FASTA         (H6)
   build_upstream/downstream/proximal_pangenome   5'/3' UTR pangenomes
   validate_upstream/downstream/proximal_table_direct   the recorded UTRs searched in the genomes -> HIP (csrc/scan.hip)
+  validate_table_against_fasta, validate_allele/upstream/downstream_table   every FASTA record looked up among the
+                                   non-redundant sequences -> HIP (csrc/dict.hip)
 
 Same names, positional order, defaults, intermediate files and return values.
 The only behavioural differences are deliberate: a failing
@@ -1363,3 +1365,268 @@ def validate_downstream_table_direct(df_downstream, genome_fna_paths, nr_downstr
     wrapper; fixed in the same way). Returns the number of missing sequences."""
     return validate_proximal_table_direct(df_downstream, genome_fna_paths, nr_downstream_fna, limits, 'downstream', log_group,
                                           ctx)
+
+
+# ---------------------------------------------------------------------------
+# a table against the FASTA files it was built from (reference :1333-1546): every record of every genome is looked up among
+# the non-redundant sequences -- exact look-ups of whole byte strings on the device (csrc/dict.hip, DESIGN.md 6h) -- and
+# the names found are compared with the table's column as two bitmaps
+# ---------------------------------------------------------------------------
+TABLE_FASTA_BATCH_BYTES = 256 << 20     # key bytes of the genomes whose records share one dict_query call
+_TABLE_FASTA_AHEAD = 8                  # genomes parsed ahead of the one being assembled
+_STR_ONLY_SPACE = bytes(range(0x1c, 0x20)) + b'\r'   # what str.strip() / universal newlines treat differently from bytes
+_BYTES_SPACE = b' \t\x0b\x0c'
+
+
+def _fasta_records(path):
+    """(headers: list of str, sequences: list of bytes) of the records of a FASTA file as validate_table_against_fasta reads
+    it (:1480-1489, :1521-1530): text mode, a record starts at a line whose first character is '>', its header is
+    line[1:].strip() -- the whole line -- and its sequence the stripped lines joined (as UTF-8 here: the reference hashes
+    seq.encode('utf-8')). Lines before the first '>' are a record with the header ''; a record without any line is skipped,
+    one whose lines are all blank has the sequence ''. A file of plain ASCII without carriage returns and without the
+    separators 0x1c-0x1f, which only str.strip() strips, is cut up as bytes; any other goes through Python's text layer."""
+    with open(path, 'rb') as f:
+        data = f.read()
+    if not data.isascii() or data.translate(None, _STR_ONLY_SPACE) != data:
+        return _fasta_records_text(path)
+    headers, seqs = [], []
+    if not data:
+        return headers, seqs
+    chunks = data.split(b'\n>')
+    if data[:1] == b'>':
+        chunks[0] = chunks[0][1:]
+    else:
+        chunks[0] = b'\n' + chunks[0]                     # an empty header line in front of the leading lines
+    if chunks[-1].endswith(b'\n'):
+        chunks[-1] = chunks[-1][:-1]                      # the file's last newline ends a line, it does not begin one
+    for chunk in chunks:
+        nl = chunk.find(b'\n')
+        if nl < 0:
+            continue                                      # a header and no line
+        body = chunk[nl + 1:]
+        if body.translate(None, _BYTES_SPACE) == body:
+            seqs.append(body.replace(b'\n', b''))
+        else:
+            seqs.append(b''.join([line.strip() for line in body.split(b'\n')]))
+        headers.append(chunk[:nl].strip().decode('ascii'))
+    return headers, seqs
+
+
+def _fasta_records_text(path):
+    """_fasta_records through Python's text-mode reading and str.strip(), statement by statement as the reference."""
+    headers, seqs = [], []
+    with open(path, 'r') as f:
+        header, blocks = '', []
+        for line in f:
+            if line[0] == '>':
+                if blocks:
+                    headers.append(header)
+                    seqs.append(''.join(blocks).encode('utf-8'))
+                header, blocks = line[1:].strip(), []
+            else:
+                blocks.append(line.strip())
+        if blocks:
+            headers.append(header)
+            seqs.append(''.join(blocks).encode('utf-8'))
+    return headers, seqs
+
+
+def _feature_to_allele(allele_names):
+    """feature -> allele of an allele names file (:1453-1466): allele TAB feature TAB feature ...; a feature with exactly
+    two '|' loses everything from the last one (PATRIC's locus tags); the last line that names a feature wins."""
+    out = {}
+    with open(allele_names, 'r') as f:
+        for line in f:
+            data = line.strip().split('\t')
+            for feature in data[1:]:
+                if feature.count('|') == 2:
+                    feature = feature[:feature.rindex('|')]
+                out[feature] = data[0]
+    return out
+
+
+def _cells_equal_to_one(table, who):
+    """(rows, cols, index labels, column labels) of the cells validate_table_against_fasta counts as present: a
+    LightSparseDataFrame by the rule of _table_cells (stored entries, all 1); of a pandas frame the cells that == 1, any
+    other value and NaN being absent and nothing raised (the reference's df_ga == 1, :1538)."""
+    if isinstance(table, sparse_utils.LightSparseDataFrame):
+        return _table_cells(table, who, notna=False)
+    if not (hasattr(table, 'index') and hasattr(table, 'columns') and hasattr(table, 'values')):
+        raise TypeError(who + ' takes a LightSparseDataFrame or a pandas DataFrame')
+    rows, cols = np.nonzero(np.asarray(table.values == 1, dtype=bool).reshape(len(table.index), len(table.columns)))
+    return rows.astype(np.int32), cols.astype(np.int32), np.asarray(table.index), np.asarray(table.columns)
+
+
+def _blob(strings):
+    """(blob uint8, offsets uint64 [n + 1]) of a list of bytes objects"""
+    offsets = np.zeros(len(strings) + 1, dtype=np.uint64)
+    if strings:
+        np.cumsum(np.fromiter(map(len, strings), dtype=np.uint64, count=len(strings)), out=offsets[1:])
+    return np.frombuffer(b''.join(strings), dtype=np.uint8), offsets
+
+
+def _genome_keys(path, feature_to_allele, suffix_of):
+    """The look-up keys of a genome file's records (:1494-1504): the sequence, and where the record's header -- cut at
+    '_upstream(' and then at '_downstream(' -- is a known feature, the sequence + trim_variant(its allele)."""
+    headers, seqs = _fasta_records(path)
+    if feature_to_allele is not None:
+        for i, header in enumerate(headers):
+            allele = feature_to_allele.get(header.split('_upstream(')[0].split('_downstream(')[0])
+            if allele is not None:
+                suffix = suffix_of.get(allele)
+                if suffix is None:
+                    suffix = suffix_of[allele] = trim_variant(allele).encode('utf-8')
+                seqs[i] = seqs[i] + suffix
+    return seqs
+
+
+def validate_table_against_fasta(df_features, genome_fasta_paths, features_fasta, allele_names=None, log_group=1, ctx=None):
+    """Verifies that a feature x genome table holds, for every genome, exactly the features whose sequences the genome's
+    FASTA file holds (reference :1418-1546): CDS or non-coding allele tables against the FAA / FNA files they were built
+    from, and with allele_names (the file build_cds_pangenome writes) upstream / downstream tables against the extracted
+    UTR files, where sequence AND gene must agree: the key is then the sequence followed by the feature's name without its
+    variant. Prints what the reference prints, byte for byte; returns the number of inconsistent genomes (the reference
+    returns None).
+
+    df_features: LightSparseDataFrame or .npz path (stored entries, which must all be 1), pandas frame or csv / pickle path
+    (a cell is present iff it == 1). Genomes are taken in sorted(genome_fasta_paths) order; a genome's column is the file's
+    name without directory and extension or, if that is no column, that name without its last '_' piece (KeyError if
+    neither is). The reference's quirks are kept: of two non-redundant records with one key the later header is the
+    feature (and `COLLISION: <header>` is printed), `Missing Features:` is always 0, lines before the first '>' are a record
+    named '', a record of blank lines is the sequence '', a header followed by a header is no record. When a genome's file
+    is missing or is no column, what the genomes before it printed comes first, then its `Validating` line if due, then
+    FileNotFoundError / KeyError.
+
+    The reference compares SHA-256 digests of the keys; here the keys' bytes are compared, exactly, on the device
+    (csrc/dict.hip: one dict_load of the non-redundant keys, one dict_query per batch of genomes bounded by
+    TABLE_FASTA_BATCH_BYTES, one genome_sets_diff at the end). The two agree unless SHA-256 collides. The next genomes are
+    parsed on a host thread while the device works. There is no CPU fallback."""
+    import collections
+    from concurrent.futures import ThreadPoolExecutor
+    who = 'validate_table_against_fasta'
+    rows, cols, labels, columns = _cells_equal_to_one(_load_table(df_features), who)
+    if ctx is None:
+        from . import _native
+        ctx = _native.default_context()
+
+    feature_to_allele = None
+    if allele_names:
+        print('Loading feature names...')
+        feature_to_allele = _feature_to_allele(allele_names)
+
+    print('Loading non-redundant sequences...')
+    nr_headers, nr_keys = _fasta_records(features_fasta)
+    if allele_names is not None:
+        nr_keys = [seq + trim_variant(header).encode('utf-8') for header, seq in zip(nr_headers, nr_keys)]
+    first = np.asarray(ctx.dict_load(*_blob(nr_keys)))
+    repeated = np.flatnonzero(first != np.arange(first.size))
+    for k in repeated.tolist():
+        print('COLLISION:', nr_headers[k])
+    print('Non-redundant sequences:', first.size - repeated.size)
+
+    # names -> rows of the two bitmaps: a table label is its first row, then the non-redundant headers that are no label
+    name_id = {}
+    for r, label in enumerate(labels.tolist()):
+        name_id.setdefault(label, r)
+    n_names = labels.size
+    name_of_key = np.empty(len(nr_headers), dtype=np.int32)
+    for k, header in enumerate(nr_headers):
+        at = name_id.get(header)
+        if at is None:
+            at = name_id[header] = n_names
+            n_names += 1
+        name_of_key[k] = at
+    first_row = np.fromiter((name_id[label] for label in labels.tolist()), dtype=np.int32, count=labels.size)
+    column_of = {}
+    for j, label in enumerate(columns.tolist()):
+        column_of.setdefault(label, j)
+    order = np.argsort(cols, kind='stable')
+    rows, cols = rows[order], cols[order]
+    col_start = np.searchsorted(cols, np.arange(columns.size + 1))
+
+    paths = sorted(genome_fasta_paths)
+    suffix_of = {}
+    genome_names = []                                     # of the genomes whose records were looked up
+    a_rows, a_genomes, b_rows, b_genomes = [], [], [], []
+    failure = None                                        # the exception the reference raises at genome len(genome_names)
+
+    def flush(batch):
+        """one dict_query for the records of the genomes in `batch`: (genome number, keys)"""
+        keys = [key for _, genome_keys in batch for key in genome_keys]
+        if not keys:
+            return
+        last = np.asarray(ctx.dict_query(*_blob(keys)))
+        genome_of = np.repeat(np.array([g for g, _ in batch], dtype=np.int32),
+                              np.array([len(k) for _, k in batch], dtype=np.int64))
+        hit = last >= 0
+        b_rows.append(name_of_key[last[hit]])
+        b_genomes.append(genome_of[hit])
+
+    with ThreadPoolExecutor(max_workers=1) as pool:
+        pending = collections.deque()
+        submitted = 0
+        batch, batch_bytes = [], 0
+        for g, path in enumerate(paths):
+            while submitted < len(paths) and len(pending) < _TABLE_FASTA_AHEAD:
+                pending.append(pool.submit(_genome_keys, paths[submitted], feature_to_allele, suffix_of))
+                submitted += 1
+            try:
+                genome_keys = pending.popleft().result()
+            except Exception as e:                        # re-raised below, after the lines of the genomes before this one
+                failure = e
+            if failure is None:
+                genome = __get_genome_from_filename__(path)
+                if genome not in column_of:
+                    genome = '_'.join(genome.split('_')[:-1])
+                if genome not in column_of:
+                    failure = KeyError(genome)
+            if failure is not None:
+                for ahead in pending:
+                    ahead.cancel()
+                break
+            genome_names.append(genome)
+            j = column_of[genome]
+            a_rows.append(first_row[rows[col_start[j]:col_start[j + 1]]])
+            a_genomes.append(np.full(col_start[j + 1] - col_start[j], g, dtype=np.int32))
+            n_bytes = sum(map(len, genome_keys))
+            if batch and batch_bytes + n_bytes > TABLE_FASTA_BATCH_BYTES:
+                flush(batch)
+                batch, batch_bytes = [], 0
+            batch.append((g, genome_keys))
+            batch_bytes += n_bytes
+        flush(batch)
+
+    n_genomes = len(genome_names)
+    if n_genomes:
+        cat = lambda parts: np.concatenate(parts) if parts else np.zeros(0, dtype=np.int32)      # noqa: E731
+        table_only, genome_only = ctx.genome_sets_diff(cat(a_rows), cat(a_genomes), cat(b_rows), cat(b_genomes), n_names,
+                                                       n_genomes)
+    inconsistencies = 0
+    for g in range(n_genomes + (failure is not None)):
+        if (g + 1) % log_group == 0:
+            print('Validating genome', g + 1, ':', paths[g])
+        if g == n_genomes:
+            raise failure
+        if table_only[g] or genome_only[g]:
+            inconsistencies += 1
+            print(genome_names[g], '\t', 'Table only:', int(table_only[g]), '\t', 'Genome only:', int(genome_only[g]))
+    print('Missing Features:', 0)                         # (the reference increments a copy, :1494-1512)
+    print('Feature Table Inconsistencies:', inconsistencies)
+    return inconsistencies
+
+
+def validate_allele_table(df_alleles, genome_fasta_paths, alleles_fasta, log_group=1, ctx=None):
+    """validate_table_against_fasta without allele names: an allele x genome table, CDS or non-coding, against the FAA / FNA
+    files of the genomes and the non-redundant sequences (reference :1391-1415)."""
+    return validate_table_against_fasta(df_alleles, genome_fasta_paths, alleles_fasta, None, log_group, ctx)
+
+
+def validate_upstream_table(df_upstream, upstream_fna_paths, nr_upstream_fna, allele_names, log_group=1, ctx=None):
+    """validate_table_against_fasta for an upstream x genome table and the extracted upstream sequences of every genome;
+    allele_names tells conserved UTRs of different genes apart (reference :1333-1359)."""
+    return validate_table_against_fasta(df_upstream, upstream_fna_paths, nr_upstream_fna, allele_names, log_group, ctx)
+
+
+def validate_downstream_table(df_downstream, downstream_fna_paths, nr_downstream_fna, allele_names, log_group=1, ctx=None):
+    """validate_table_against_fasta for a downstream x genome table (reference :1362-1388)."""
+    return validate_table_against_fasta(df_downstream, downstream_fna_paths, nr_downstream_fna, allele_names, log_group, ctx)
