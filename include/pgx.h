@@ -542,7 +542,9 @@ int pgx_fcd_coverage(pgx_ctx *ctx, const int32_t *rows, const int32_t *genomes, 
  *                     row ascending: block_of_row[r] (n_rows entries), rep_row[b] = the first row of block b (room for
  *                     n_rows entries, *out_n_blocks used). All rows without a genome form one block, unless
  *   PGX_ASSOC_DROP_EMPTY  those rows take no part (block_of_row = -1): the blocks of the table without its empty rows.
- * The result does not depend on the order in which the device's waves run. The bitmap is never written.
+ * The result does not depend on the order in which the device's waves run. The bitmap is never written. n_selected = 0
+ * (col_map may then be NULL) is the table without a column: incidence and tp are 0 and all rows are empty.
+ * PGX_ASSOC_NARROW_HASH (a test seam) keeps only the low 3 bits of every hash: same results, every probe collides.
  *   pgx_assoc            HOST COO coordinates of the table; out_duplicates as pgx_presence_bitmap (may be NULL): with
  *                        duplicate coordinates nothing is computed
  *   pgx_assoc_resident   the table is read from the bitmap a pipeline left resident (pgx_bitmap_from_clusters): row i of
@@ -553,6 +555,7 @@ int pgx_fcd_coverage(pgx_ctx *ctx, const int32_t *rows, const int32_t *genomes, 
  * out_tp / masks may be NULL with n_targets = 0; the block arrays may be NULL without PGX_ASSOC_BLOCKS. n_rows < 2^30. */
 #define PGX_ASSOC_BLOCKS 1u
 #define PGX_ASSOC_DROP_EMPTY 2u
+#define PGX_ASSOC_NARROW_HASH 4u   /* keep only the low 3 bits of every hash: same results, every probe collides */
 size_t pgx_assoc_workspace_bytes(uint32_t n_rows, uint32_t n_selected);
 int pgx_assoc(pgx_ctx *ctx, const int32_t *rows, const int32_t *genomes, uint64_t n_records, uint32_t n_rows,
               uint32_t n_genomes, const int32_t *col_map, uint32_t n_selected, const uint64_t *masks, uint32_t n_targets,

@@ -71,6 +71,7 @@ FCD_OVERLAP, FCD_DIM_BALANCE = 1, 2    # PGX_FCD_OVERLAP, PGX_FCD_DIM_BALANCE
 BERNOULLI_CD_LOGS = 1                  # PGX_BERNOULLI_CD_LOGS
 ASSOC_BLOCKS, ASSOC_DROP_EMPTY = 1, 2  # PGX_ASSOC_BLOCKS, PGX_ASSOC_DROP_EMPTY
 DICT_NARROW_HASH = 1                   # PGX_DICT_NARROW_HASH
+ASSOC_NARROW_HASH = 4                  # PGX_ASSOC_NARROW_HASH
 
 
 # every symbol include/pgx.h declares: (restype, argtypes)
@@ -661,7 +662,7 @@ class Context(object):
 
     # -- association screen (sparse_utils.compress_rows*, ml_pipelines.contingency_tables_from_sparse) -------------------
     @staticmethod
-    def _assoc_args(n_rows, n_genomes, col_map, masks, blocks, drop_empty):
+    def _assoc_args(n_rows, n_genomes, col_map, masks, blocks, drop_empty, narrow_hash):
         n_rows, n_genomes = int(n_rows), int(n_genomes)
         if col_map is not None:
             col_map = np.ascontiguousarray(col_map, dtype=np.int32)
@@ -675,7 +676,8 @@ class Context(object):
             if masks.ndim != 2 or masks.shape[1] != words:
                 raise ValueError('masks must be [n_targets, %d] words' % words)
             n_targets = int(masks.shape[0])
-        flags = (ASSOC_BLOCKS if blocks else 0) | (ASSOC_DROP_EMPTY if blocks and drop_empty else 0)
+        flags = ((ASSOC_BLOCKS if blocks else 0) | (ASSOC_DROP_EMPTY if blocks and drop_empty else 0) |
+                 (ASSOC_NARROW_HASH if narrow_hash else 0))
         out = {'tp': np.zeros((n_targets, n_rows), dtype=np.uint32), 'incidence': np.zeros(n_rows, dtype=np.uint32),
                'block_of_row': np.full(n_rows if blocks else 0, -1, dtype=np.int32),
                'rep_row': np.zeros(n_rows if blocks else 0, dtype=np.int32)}
@@ -688,12 +690,15 @@ class Context(object):
             out['block_of_row'] = None
         return out
 
-    def assoc(self, rows, genomes, n_rows, n_genomes, col_map=None, masks=None, blocks=False, drop_empty=False):
+    def assoc(self, rows, genomes, n_rows, n_genomes, col_map=None, masks=None, blocks=False, drop_empty=False,
+              narrow_hash=False):
         """({'tp' uint32 [n_targets, n_rows], 'incidence' uint32 [n_rows], 'block_of_row' int32 [n_rows], 'rep_row' int32
         [n_blocks]}, duplicates) of the binary table with the given COO coordinates, restricted to the genomes col_map
-        (pgx.h: pgx_assoc); with duplicate coordinates nothing is computed and the dict is None."""
+        (pgx.h: pgx_assoc); with duplicate coordinates nothing is computed and the dict is None. narrow_hash: the test seam
+        ASSOC_NARROW_HASH."""
         rows, genomes = _coo_args(rows, genomes)
-        col_map, n_sel, masks, n_targets, flags, out = self._assoc_args(n_rows, n_genomes, col_map, masks, blocks, drop_empty)
+        col_map, n_sel, masks, n_targets, flags, out = self._assoc_args(n_rows, n_genomes, col_map, masks, blocks, drop_empty,
+                                                                        narrow_hash)
         n_blocks, dup = C.c_uint32(0), C.c_uint64(0)
         check(lib().pgx_assoc(self._h, _ptr(rows), _ptr(genomes), rows.size, int(n_rows), int(n_genomes), _ptr(col_map), n_sel,
                               _ptr(masks), n_targets, flags, _ptr(out['tp']), _ptr(out['incidence']),
@@ -702,12 +707,13 @@ class Context(object):
             return None, int(dup.value)
         return self._assoc_out(out, blocks, n_blocks), 0
 
-    def assoc_resident(self, token, row_map, n_genomes, col_map=None, masks=None, blocks=False, drop_empty=False):
+    def assoc_resident(self, token, row_map, n_genomes, col_map=None, masks=None, blocks=False, drop_empty=False,
+                       narrow_hash=False):
         """The same from the bitmap a pipeline left resident under `token` (not modified): row i of the table is row
         row_map[i] of it. Raises PgxError when the token is stale."""
         row_map = np.ascontiguousarray(row_map, dtype=np.int32)
         col_map, n_sel, masks, n_targets, flags, out = self._assoc_args(row_map.size, n_genomes, col_map, masks, blocks,
-                                                                        drop_empty)
+                                                                        drop_empty, narrow_hash)
         n_blocks = C.c_uint32(0)
         check(lib().pgx_assoc_resident(self._h, int(token), _ptr(row_map), row_map.size, int(n_genomes), _ptr(col_map), n_sel,
                                        _ptr(masks), n_targets, flags, _ptr(out['tp']), _ptr(out['incidence']),
@@ -715,9 +721,10 @@ class Context(object):
         return self._assoc_out(out, blocks, n_blocks)
 
     def assoc_dev(self, d_bits, n_rows, n_genomes, d_col_map, n_selected, d_masks, n_targets, d_tp, d_incidence,
-                  d_block_of_row, d_rep_row, d_ws, ws_bytes, blocks=True, drop_empty=False, stream=0):
+                  d_block_of_row, d_rep_row, d_ws, ws_bytes, blocks=True, drop_empty=False, stream=0, narrow_hash=False):
         """The same on device memory (raw device addresses; synchronises `stream`, see pgx.h); returns n_blocks."""
-        flags = (ASSOC_BLOCKS if blocks else 0) | (ASSOC_DROP_EMPTY if blocks and drop_empty else 0)
+        flags = ((ASSOC_BLOCKS if blocks else 0) | (ASSOC_DROP_EMPTY if blocks and drop_empty else 0) |
+                 (ASSOC_NARROW_HASH if narrow_hash else 0))
         n_blocks = C.c_uint32(0)
         check(lib().pgx_assoc_dev(self._h, d_bits, int(n_rows), int(n_genomes), d_col_map, int(n_selected), d_masks,
                                   int(n_targets), flags, d_tp, d_incidence, d_block_of_row, d_rep_row, d_ws, int(ws_bytes),

@@ -25,6 +25,13 @@
 //                        rep_row[block] = its first row
 // With PGX_ASSOC_DROP_EMPTY the rows without a genome in the selection take no part (block_of_row = -1): the blocks are
 // those of the table after drop_empty(axis='index').
+// The hash only decides where a row starts to look; a row joins a slot after its signature has been compared word for word,
+// so the blocks are exact whatever the hash does (mix64 does collide on real tables: rows that differ in bit 62 of one word
+// and bits 33 and 62 of the next) -- PGX_ASSOC_NARROW_HASH (a test seam) keeps 3 bits of it and must give the
+// same output. Under it a row's stored hash is h & 7 (two different rows collide with probability 1/8 and the compare
+// decides) and its first slot is (cap - 4 + (h & 7)) & (cap - 1): the eight start slots straddle the end of the table, so
+// every table of more than four blocks wraps from slot cap - 1 to slot 0 and a chain is as long as there are blocks (the
+// walk is then quadratic in the blocks).
 #include "pgx_internal.h"
 
 namespace {
@@ -73,7 +80,7 @@ __global__ __launch_bounds__(AS_THREADS) void assoc_sig_kernel(const unsigned lo
                                                                uint32_t n_sel, uint32_t words, uint32_t pitch,
                                                                unsigned long long *__restrict__ sig,
                                                                unsigned long long *__restrict__ hash, uint32_t *__restrict__ inc,
-                                                               uint32_t *__restrict__ status) {
+                                                               int narrow, uint32_t *__restrict__ status) {
     const uint32_t r = blockIdx.x * AS_THREADS + threadIdx.x;
     if (r >= n_rows) return;
     const uint32_t m = row_map ? (uint32_t)row_map[r] : r;
@@ -95,7 +102,7 @@ __global__ __launch_bounds__(AS_THREADS) void assoc_sig_kernel(const unsigned lo
         count += (uint32_t)__popcll(word);
         h = mix64(h, word);
     }
-    hash[r] = h;
+    hash[r] = narrow ? (h & 7ull) : h;                            // (uniform; PGX_ASSOC_NARROW_HASH)
     inc[r] = count;
     if (bad) atomicOr(status, AS_ERR_MAP);
 }
@@ -116,6 +123,7 @@ __global__ __launch_bounds__(AS_THREADS) void assoc_claim_kernel(const unsigned 
                                                                  const unsigned long long *__restrict__ hash,
                                                                  const uint32_t *__restrict__ inc, uint32_t n_rows,
                                                                  uint32_t words, uint32_t pitch, uint32_t cap, int drop_empty,
+                                                                 int narrow,
                                                                  uint32_t *__restrict__ owner, uint32_t *__restrict__ first_row,
                                                                  uint32_t *__restrict__ slot_of_row,
                                                                  uint32_t *__restrict__ status) {
@@ -124,7 +132,7 @@ __global__ __launch_bounds__(AS_THREADS) void assoc_claim_kernel(const unsigned 
     uint32_t found = AS_NONE;
     if (!(drop_empty && inc[r] == 0u)) {
         const unsigned long long h = hash[r];
-        uint32_t slot = (uint32_t)(h >> 20) & (cap - 1u);
+        uint32_t slot = (narrow ? cap - 4u + (uint32_t)(h & 7ull) : (uint32_t)(h >> 20)) & (cap - 1u);
         for (uint32_t probe = 0; probe < cap; ++probe, slot = (slot + 1u) & (cap - 1u)) {
             uint32_t o = atomicCAS(&owner[slot], AS_NONE, r);
             if (o == AS_NONE) o = r;                              // claimed
@@ -215,10 +223,11 @@ int assoc_run(pgx_ctx *ctx, const uint64_t *d_bits, uint32_t src_rows, uint32_t 
               uint32_t flags, uint32_t *d_tp, uint32_t *d_inc, int32_t *d_block, int32_t *d_rep, void *d_ws, size_t ws_bytes,
               hipStream_t stream, uint32_t *out_n_blocks) {
     PGX_REQUIRE(ctx, "NULL argument");
-    PGX_REQUIRE((flags & ~(uint32_t)(PGX_ASSOC_BLOCKS | PGX_ASSOC_DROP_EMPTY)) == 0, "unknown flag");
+    PGX_REQUIRE((flags & ~(uint32_t)(PGX_ASSOC_BLOCKS | PGX_ASSOC_DROP_EMPTY | PGX_ASSOC_NARROW_HASH)) == 0, "unknown flag");
     PGX_REQUIRE(sizes_ok(n_rows, n_genomes, n_sel, n_targets), "table too large");
-    PGX_REQUIRE(d_col_map || n_sel == n_genomes, "without a column map every genome is selected");
+    PGX_REQUIRE(d_col_map || n_sel == n_genomes || n_sel == 0, "without a column map every genome is selected");
     const bool blocks = (flags & PGX_ASSOC_BLOCKS) != 0;
+    const int narrow = (flags & PGX_ASSOC_NARROW_HASH) != 0;
     if (out_n_blocks) *out_n_blocks = 0;
     if (n_rows == 0) return PGX_OK;
     PGX_REQUIRE(d_bits && d_ws && d_inc, "NULL argument");
@@ -243,7 +252,7 @@ int assoc_run(pgx_ctx *ctx, const uint64_t *d_bits, uint32_t src_rows, uint32_t 
         ProfScope prof(ctx, "assoc_sig_kernel", stream);
         assoc_sig_kernel<<<row_blocks, AS_THREADS, 0, stream>>>((const unsigned long long *)d_bits, stride, src_rows, n_genomes,
                                                                 d_row_map, d_col_map, n_rows, n_sel, g.words, g.pitch, sig, hash,
-                                                                d_inc, status);
+                                                                d_inc, narrow, status);
     }
     PGX_HIP(hipGetLastError());
     if (n_targets) {
@@ -257,8 +266,8 @@ int assoc_run(pgx_ctx *ctx, const uint64_t *d_bits, uint32_t src_rows, uint32_t 
         {
             ProfScope prof(ctx, "assoc_claim_kernel", stream);
             assoc_claim_kernel<<<row_blocks, AS_THREADS, 0, stream>>>(sig, hash, d_inc, n_rows, g.words, g.pitch, g.cap,
-                                                                      (flags & PGX_ASSOC_DROP_EMPTY) != 0, owner, first_row,
-                                                                      slot_of_row, status);
+                                                                      (flags & PGX_ASSOC_DROP_EMPTY) != 0, narrow, owner,
+                                                                      first_row, slot_of_row, status);
         }
         PGX_HIP(hipGetLastError());
         {
@@ -301,7 +310,7 @@ int assoc_staged(pgx_ctx *ctx, const uint64_t *d_bits, uint32_t src_rows, uint32
     PGX_REQUIRE(out_inc || n_rows == 0, "NULL argument");
     PGX_REQUIRE(n_targets == 0 || n_rows == 0 || (masks && out_tp), "NULL argument");
     PGX_REQUIRE(!blocks || (out_n_blocks && (n_rows == 0 || (out_block && out_rep))), "NULL argument");
-    PGX_REQUIRE(col_map || n_sel == n_genomes, "without a column map every genome is selected");
+    PGX_REQUIRE(col_map || n_sel == n_genomes || n_sel == 0, "without a column map every genome is selected");
     for (uint32_t j = 0; col_map && j < n_sel; ++j)
         PGX_REQUIRE(col_map[j] >= 0 && (uint32_t)col_map[j] < n_genomes, "column map entry out of range");
     for (uint32_t i = 0; row_map && i < n_rows; ++i)

@@ -31,6 +31,17 @@ def blocks(X):
     return rank[inverse.ravel()], np.sort(first).astype(np.int64)
 
 
+def blocks_drop_empty(X):
+    """blocks() of the table without its empty rows (PGX_ASSOC_DROP_EMPTY), in the row numbers of the whole table:
+    block_of_row is -1 for an empty row, rep_row holds rows of X."""
+    X = np.asarray(X) != 0
+    kept = np.flatnonzero(X.any(axis=1))
+    b, rep = blocks(X[kept])
+    block_of_row = np.full(X.shape[0], -1, dtype=np.int64)
+    block_of_row[kept] = b
+    return block_of_row, kept[rep].astype(np.int64)
+
+
 def definitions(block_of_row, n_blocks):
     """[rows of block b, ascending] for every block; rows of block -1 belong to none."""
     block_of_row = np.asarray(block_of_row, dtype=np.int64)
