@@ -52,17 +52,16 @@ AssocGeom make_geom(uint32_t n_rows, uint32_t n_sel) {
     g.cap = 64;
     while ((uint64_t)g.cap < 2ull * n_rows) g.cap <<= 1;          // (n_rows < 2^31 / 2: checked by the callers)
     g.flag_words = g.pitch / 64;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    g.off_sig = take((size_t)g.words * g.pitch * 8);
-    g.off_hash = take((size_t)g.pitch * 8);
-    g.off_table = take((size_t)g.cap * 8);                        // owner[cap] then first_row[cap], both filled with 0xFF
-    g.off_slot = take((size_t)g.pitch * 4);
-    g.off_rep = take((size_t)g.pitch * 4);
-    g.off_flags = take((size_t)g.flag_words * 8);
-    g.off_prefix = take((size_t)g.flag_words * 4);
-    g.off_status = take(16);
-    g.bytes = off;
+    WsLayout ws;
+    g.off_sig = ws.take((size_t)g.words * g.pitch * 8);
+    g.off_hash = ws.take((size_t)g.pitch * 8);
+    g.off_table = ws.take((size_t)g.cap * 8);                     // owner[cap] then first_row[cap], both filled with 0xFF
+    g.off_slot = ws.take((size_t)g.pitch * 4);
+    g.off_rep = ws.take((size_t)g.pitch * 4);
+    g.off_flags = ws.take((size_t)g.flag_words * 8);
+    g.off_prefix = ws.take((size_t)g.flag_words * 4);
+    g.off_status = ws.take(16);
+    g.bytes = ws.off;
     return g;
 }
 
@@ -204,14 +203,6 @@ __global__ __launch_bounds__(AS_THREADS) void assoc_assign_kernel(const uint32_t
     if (first == r && id < n_rows) rep_row[id] = (int32_t)r;
 }
 
-// device buffers of the host-pointer entry points (slots after fcd's); host scratch slot 130
-enum { AS_SLOT_BITS = 130, AS_SLOT_ROWS, AS_SLOT_GENOMES, AS_SLOT_CNT, AS_SLOT_WS, AS_SLOT_RMAP, AS_SLOT_CMAP, AS_SLOT_MASKS,
-       AS_SLOT_TP, AS_SLOT_INC, AS_SLOT_BLOCK, AS_SLOT_REP };
-constexpr int AS_HOST_STATUS = 130;
-struct AsBuf : DevBuf {
-    AsBuf(pgx_ctx *c, int s) { ctx = c; slot = s; }
-};
-
 bool sizes_ok(uint32_t n_rows, uint32_t n_genomes, uint32_t n_sel, uint32_t n_targets) {
     return n_rows < (1u << 30) && n_genomes < (1u << 31) && n_sel < (1u << 31) && n_targets <= 65535u;
 }
@@ -319,7 +310,7 @@ int assoc_staged(pgx_ctx *ctx, const uint64_t *d_bits, uint32_t src_rows, uint32
     if (n_rows == 0) return PGX_OK;
     hipStream_t stream = ctx->stream;
     const AssocGeom g = make_geom(n_rows, n_sel);
-    AsBuf d_ws(ctx, AS_SLOT_WS), d_rmap(ctx, AS_SLOT_RMAP), d_cmap(ctx, AS_SLOT_CMAP), d_masks(ctx, AS_SLOT_MASKS),
+    DevBuf d_ws(ctx, AS_SLOT_WS), d_rmap(ctx, AS_SLOT_RMAP), d_cmap(ctx, AS_SLOT_CMAP), d_masks(ctx, AS_SLOT_MASKS),
         d_tp(ctx, AS_SLOT_TP), d_inc(ctx, AS_SLOT_INC), d_block(ctx, AS_SLOT_BLOCK), d_rep(ctx, AS_SLOT_REP);
     PGX_HIP(d_ws.alloc(g.bytes));
     PGX_HIP(d_rmap.alloc((size_t)n_rows * 4));
@@ -357,11 +348,10 @@ int assoc_host(pgx_ctx *ctx, const int32_t *rows, const int32_t *genomes, uint64
     PGX_REQUIRE(n_records == 0 || (rows && genomes), "NULL record arrays");
     PGX_REQUIRE(sizes_ok(n_rows, n_genomes, n_sel, n_targets), "table too large");
     PGX_HIP(hipSetDevice(ctx->device_id));
-    AsBuf d_bits(ctx, AS_SLOT_BITS), d_cnt(ctx, AS_SLOT_CNT);
-    int rc = pgx_upload_and_build_bitmap(ctx, rows, genomes, n_records, n_rows, n_genomes, AS_SLOT_ROWS, AS_SLOT_GENOMES, d_bits,
-                                         d_cnt);
+    DevBuf d_bits(ctx, AS_SLOT_BITS), d_cnt(ctx, AS_SLOT_CNT);
     uint64_t dup = 0;
-    if (rc == PGX_OK) rc = pgx_read_record_counters(ctx, d_cnt, &dup);
+    const int rc = pgx_load_coo_bitmap(ctx, rows, genomes, n_records, n_rows, n_genomes, AS_SLOT_ROWS, AS_SLOT_GENOMES, d_bits,
+                                       d_cnt, &dup);
     if (rc != PGX_OK) return rc;
     if (out_duplicates) *out_duplicates = dup;
     if (out_n_blocks) *out_n_blocks = 0;
@@ -375,14 +365,13 @@ int assoc_resident(pgx_ctx *ctx, uint64_t token, const int32_t *row_map, uint32_
                    uint32_t *out_tp, uint32_t *out_inc, int32_t *out_block, int32_t *out_rep, uint32_t *out_n_blocks) {
     PGX_REQUIRE(ctx, "NULL argument");
     PGX_REQUIRE(n_rows == 0 || row_map, "NULL row map");
-    PGX_REQUIRE(token != 0 && token == ctx->resident_token && n_genomes == ctx->resident_genomes,
-                "the bitmap of that token is not resident any more");
+    ResidentBitmap src;
+    const int rc = pgx_resident_bitmap(ctx, token, n_genomes, &src);
+    if (rc != PGX_OK) return rc;
     PGX_REQUIRE(sizes_ok(n_rows, n_genomes, n_sel, n_targets), "table too large");
     PGX_HIP(hipSetDevice(ctx->device_id));
-    AsBuf d_src(ctx, PGX_SLOT_RESIDENT);
-    PGX_HIP(d_src.alloc((size_t)n_genomes * pgx_bitmap_stride_words(ctx->resident_genes) * 8));   // (a view: no allocation)
-    return assoc_staged(ctx, d_src.as<uint64_t>(), ctx->resident_genes, n_genomes, row_map, n_rows, col_map, n_sel, masks,
-                        n_targets, flags, out_tp, out_inc, out_block, out_rep, out_n_blocks);
+    return assoc_staged(ctx, src.d_bits, src.n_genes, n_genomes, row_map, n_rows, col_map, n_sel, masks, n_targets, flags,
+                        out_tp, out_inc, out_block, out_rep, out_n_blocks);
 }
 
 }  // namespace

@@ -45,8 +45,6 @@ struct BernGeom {
     size_t off_dp, off_ll, off_cnt_a, off_dq, off_cnt_b, off_terms, bytes;   // workspace layout
 };
 
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 BernGeom make_geom(uint32_t G, uint32_t S) {
     BernGeom g;
     g.stride = pgx_bitmap_stride_words(G);
@@ -60,14 +58,15 @@ BernGeom make_geom(uint32_t G, uint32_t S) {
     slabs = std::min(ceil_div_u32(BN_TARGET_WAVES, waves_b), std::max(1u, g.words));
     g.b_span = std::max(1u, ceil_div_u32(g.words, slabs));
     g.b_slabs = std::max(1u, ceil_div_u32(g.words, g.b_span));
-    size_t o = 256;                                          // [0, 256): the mode word
-    g.off_dp = o;    o = align256(o + (size_t)g.a_slabs * G * 8);
-    g.off_ll = o;    o = align256(o + (size_t)g.a_slabs * G * 8);
-    g.off_cnt_a = o; o = align256(o + (size_t)g.a_slabs * G * 4);
-    g.off_dq = o;    o = align256(o + (size_t)g.b_slabs * S * 8);
-    g.off_cnt_b = o; o = align256(o + (size_t)g.b_slabs * S * 4);
-    g.off_terms = o; o = align256(o + ((size_t)G + S) * 8);
-    g.bytes = o;
+    WsLayout ws;
+    ws.take(256);                                            // [0, 256): the mode word
+    g.off_dp = ws.take((size_t)g.a_slabs * G * 8);
+    g.off_ll = ws.take((size_t)g.a_slabs * G * 8);
+    g.off_cnt_a = ws.take((size_t)g.a_slabs * G * 4);
+    g.off_dq = ws.take((size_t)g.b_slabs * S * 8);
+    g.off_cnt_b = ws.take((size_t)g.b_slabs * S * 4);
+    g.off_terms = ws.take(((size_t)G + S) * 8);
+    g.bytes = ws.off;
     return g;
 }
 
@@ -242,35 +241,6 @@ __global__ __launch_bounds__(1024) void bern_total_kernel(const double *__restri
     if (threadIdx.x == 0) out[0] = s[0];
 }
 
-// bitmap of the table's rows from the resident bitmap (rows = cluster numbers): row i of the output is row
-// row_map[i] of the input. One thread per output word.
-__global__ __launch_bounds__(BN_THREADS) void bern_gather_rows_kernel(const unsigned long long *__restrict__ src,
-                                                                      uint32_t src_stride, const int32_t *__restrict__ row_map,
-                                                                      uint32_t G, uint32_t S, uint32_t stride,
-                                                                      unsigned long long *__restrict__ dst) {
-    const uint64_t total = (uint64_t)S * stride;
-    for (uint64_t idx = (uint64_t)blockIdx.x * BN_THREADS + threadIdx.x; idx < total;
-         idx += (uint64_t)gridDim.x * BN_THREADS) {
-        const uint32_t s = (uint32_t)(idx / stride), w = (uint32_t)(idx % stride);
-        const unsigned long long *row = src + (size_t)s * src_stride;
-        unsigned long long word = 0;
-        for (uint32_t b = 0; b < 64; ++b) {
-            const uint32_t i = w * 64 + b;
-            if (i >= G) break;
-            const uint32_t m = (uint32_t)row_map[i];
-            word |= ((row[m >> 6] >> (m & 63u)) & 1ull) << b;
-        }
-        dst[idx] = word;
-    }
-}
-
-// device buffers of the host-pointer entry points (slots after pan/core's and the Heaps fit's)
-enum { BN_SLOT_BITS = 100, BN_SLOT_ROWS, BN_SLOT_GENOMES, BN_SLOT_CNT, BN_SLOT_MAP, BN_SLOT_PQ, BN_SLOT_OUT, BN_SLOT_WS };
-static_assert(BN_SLOT_BITS == PGX_SLOT_BERN_BITS, "bernoulli_cd.hip reads the loaded table from this slot");
-struct BnBuf : DevBuf {
-    BnBuf(pgx_ctx *c, int s) { ctx = c; slot = s; }
-};
-
 int eval_dev(pgx_ctx *ctx, const uint64_t *d_bits, uint32_t G, uint32_t S, const double *d_pq, uint32_t flags,
              double *d_out, void *d_ws, size_t ws_bytes, void *stream_) {
     PGX_REQUIRE(ctx, "NULL context");
@@ -327,9 +297,9 @@ int load_coo(pgx_ctx *ctx, const int32_t *rows, const int32_t *genomes, uint64_t
     PGX_REQUIRE((uint64_t)G + S < (1ull << 31), "table too large");
     PGX_HIP(hipSetDevice(ctx->device_id));
     ctx->bern_loaded = false;
-    BnBuf d_bits(ctx, BN_SLOT_BITS), d_cnt(ctx, BN_SLOT_CNT);
-    int rc = pgx_upload_and_build_bitmap(ctx, rows, genomes, n_records, G, S, BN_SLOT_ROWS, BN_SLOT_GENOMES, d_bits, d_cnt);
-    if (rc == PGX_OK) rc = pgx_read_record_counters(ctx, d_cnt, out_duplicates);
+    DevBuf d_bits(ctx, PGX_SLOT_BERN_BITS), d_cnt(ctx, BN_SLOT_CNT);
+    const int rc = pgx_load_coo_bitmap(ctx, rows, genomes, n_records, G, S, BN_SLOT_ROWS, BN_SLOT_GENOMES, d_bits, d_cnt,
+                                       out_duplicates);
     if (rc != PGX_OK) return rc;
     ctx->bern_genes = G;
     ctx->bern_genomes = S;
@@ -340,29 +310,15 @@ int load_coo(pgx_ctx *ctx, const int32_t *rows, const int32_t *genomes, uint64_t
 int load_resident(pgx_ctx *ctx, uint64_t token, const int32_t *row_map, uint32_t G, uint32_t S) {
     PGX_REQUIRE(ctx, "NULL context");
     PGX_REQUIRE(G == 0 || row_map, "NULL row map");
-    PGX_REQUIRE(token != 0 && token == ctx->resident_token && S == ctx->resident_genomes,
-                "the bitmap of that token is not resident any more");
+    ResidentBitmap src;
+    int rc = pgx_resident_bitmap(ctx, token, S, &src);
+    if (rc != PGX_OK) return rc;
     PGX_REQUIRE((uint64_t)G + S < (1ull << 31), "table too large");
-    for (uint32_t i = 0; i < G; ++i)
-        PGX_REQUIRE(row_map[i] >= 0 && (uint32_t)row_map[i] < ctx->resident_genes, "row map entry out of range");
     PGX_HIP(hipSetDevice(ctx->device_id));
-    ctx->bern_loaded = false;
-    const uint32_t stride = pgx_bitmap_stride_words(G);
-    const uint32_t src_stride = pgx_bitmap_stride_words(ctx->resident_genes);
-    BnBuf d_src(ctx, PGX_SLOT_RESIDENT), d_map(ctx, BN_SLOT_MAP), d_bits(ctx, BN_SLOT_BITS);
-    PGX_HIP(d_src.alloc((size_t)S * src_stride * 8));       // (a view of the resident slot: no allocation)
-    PGX_HIP(d_map.alloc((size_t)G * 4));
-    PGX_HIP(d_bits.alloc((size_t)S * stride * 8));
-    if (G) PGX_HIP(hipMemcpyAsync(d_map.p, row_map, (size_t)G * 4, hipMemcpyHostToDevice, ctx->stream));
-    const uint64_t total = (uint64_t)S * stride;
-    if (total) {
-        const uint64_t want = (total + BN_THREADS - 1) / BN_THREADS;
-        ProfScope prof(ctx, "bern_gather_rows_kernel", ctx->stream);
-        bern_gather_rows_kernel<<<(uint32_t)(want < 8192 ? want : 8192), BN_THREADS, 0, ctx->stream>>>(
-            d_src.as<unsigned long long>(), src_stride, d_map.as<int32_t>(), G, S, stride, d_bits.as<unsigned long long>());
-        PGX_HIP(hipGetLastError());
-    }
-    PGX_HIP(hipStreamSynchronize(ctx->stream));
+    DevBuf d_map(ctx, BN_SLOT_MAP), d_bits(ctx, PGX_SLOT_BERN_BITS);
+    rc = pgx_gather_resident(ctx, src, row_map, nullptr, G, S, d_map, nullptr, d_bits, "bern_gather_rows_kernel");
+    if (rc != PGX_OK && rc != PGX_ERR_INVALID) ctx->bern_loaded = false;   // (a refused map leaves the loaded table alone)
+    if (rc != PGX_OK) return rc;
     ctx->bern_genes = G;
     ctx->bern_genomes = S;
     ctx->bern_loaded = true;
@@ -376,14 +332,14 @@ int eval_loaded(pgx_ctx *ctx, const double *pq, uint32_t flags, double *out) {
     const uint32_t G = ctx->bern_genes, S = ctx->bern_genomes;
     const size_t n = (size_t)G + S;
     const size_t nws = make_geom(G, S).bytes;
-    BnBuf d_bits(ctx, BN_SLOT_BITS), d_pq(ctx, BN_SLOT_PQ), d_out(ctx, BN_SLOT_OUT), d_ws(ctx, BN_SLOT_WS);
-    PGX_HIP(d_bits.alloc((size_t)S * pgx_bitmap_stride_words(G) * 8));   // (a view of the loaded table)
+    DevBuf d_bits(ctx, PGX_SLOT_BERN_BITS), d_pq(ctx, BN_SLOT_PQ), d_out(ctx, BN_SLOT_OUT), d_ws(ctx, BN_SLOT_WS);
+    int rc = d_bits.view((size_t)S * pgx_bitmap_stride_words(G) * 8);    // (the loaded table)
+    if (rc != PGX_OK) return rc;
     PGX_HIP(d_pq.alloc(n * 8));
     PGX_HIP(d_out.alloc((n + 1) * 8));
     PGX_HIP(d_ws.alloc(nws));
     if (n) PGX_HIP(hipMemcpyAsync(d_pq.p, pq, n * 8, hipMemcpyHostToDevice, ctx->stream));
-    int rc = eval_dev(ctx, d_bits.as<uint64_t>(), G, S, d_pq.as<double>(), flags, d_out.as<double>(), d_ws.p, nws,
-                      ctx->stream);
+    rc = eval_dev(ctx, d_bits.as<uint64_t>(), G, S, d_pq.as<double>(), flags, d_out.as<double>(), d_ws.p, nws, ctx->stream);
     if (rc != PGX_OK) return rc;
     PGX_HIP(hipMemcpyAsync(out, d_out.p, (n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
     PGX_HIP(hipStreamSynchronize(ctx->stream));

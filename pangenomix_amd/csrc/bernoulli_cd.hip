@@ -53,25 +53,23 @@ struct CdGeom {
     size_t bern_bytes, bytes;
 };
 
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 CdGeom make_geom(uint32_t G, uint32_t S) {
     CdGeom g;
     const size_t n = (size_t)G + S;
-    size_t o = 0;
-    g.off_par = o;   o += 256;                       // the two bounds in the solver's variable
-    g.off_stats = o; o += 256;                       // 4 x u64: evaluations, most evaluations of one solve, failures
-    g.off_pq = o;    o = align256(o + n * 8);        // the solver's variables [P; Q] (or their logs)
-    g.off_ex = o;    o = align256(o + n * 8);        // log flavour: exp of them
-    g.off_cnt = o;   o = align256(o + n * 4);        // rowsum, colsum
-    g.off_evsum = o; o = align256(o + n * 4);
-    g.off_evmax = o; o = align256(o + n * 4);
-    g.off_fail = o;  o = align256(o + n * 4);
-    g.off_terms = o; o = align256(o + n * 8);        // log flavour: each row's and column's share of LL
-    g.off_eval = o;  o = align256(o + (n + 1) * 8);  // [LL; gradient] of pgx_bernoulli_eval_dev
-    g.off_bern = o;
+    WsLayout ws;
+    g.off_par = ws.take(256);                        // the two bounds in the solver's variable
+    g.off_stats = ws.take(256);                      // 4 x u64: evaluations, most evaluations of one solve, failures
+    g.off_pq = ws.take(n * 8);                       // the solver's variables [P; Q] (or their logs)
+    g.off_ex = ws.take(n * 8);                       // log flavour: exp of them
+    g.off_cnt = ws.take(n * 4);                      // rowsum, colsum
+    g.off_evsum = ws.take(n * 4);
+    g.off_evmax = ws.take(n * 4);
+    g.off_fail = ws.take(n * 4);
+    g.off_terms = ws.take(n * 8);                    // log flavour: each row's and column's share of LL
+    g.off_eval = ws.take((n + 1) * 8);               // [LL; gradient] of pgx_bernoulli_eval_dev
     g.bern_bytes = pgx_bernoulli_workspace_bytes(G, S);
-    g.bytes = align256(o + g.bern_bytes);
+    g.off_bern = ws.take(g.bern_bytes);
+    g.bytes = ws.off;
     return g;
 }
 
@@ -488,11 +486,6 @@ int cd_dev(pgx_ctx *ctx, const uint64_t *d_bits, uint32_t G, uint32_t S, const d
     return read_statistics(ctx, G, S, T);
 }
 
-enum { CD_SLOT_INIT = 180, CD_SLOT_TABLE, CD_SLOT_SOLVER, CD_SLOT_WS };
-struct CdBuf : DevBuf {
-    CdBuf(pgx_ctx *c, int s) { ctx = c; slot = s; }
-};
-
 int cd_loaded(pgx_ctx *ctx, const double *init_p, double init_q, double lo, double hi, uint32_t T, uint32_t flags,
               double *out_table, double *out_solver) {
     PGX_REQUIRE(ctx && init_p && out_table, "NULL argument");
@@ -505,9 +498,10 @@ int cd_loaded(pgx_ctx *ctx, const double *init_p, double init_q, double lo, doub
     PGX_HIP(hipSetDevice(ctx->device_id));
     const CdGeom g = make_geom(G, S);
     const size_t cells = ((size_t)G + S + 1) * ((size_t)T + 1);
-    CdBuf d_bits(ctx, PGX_SLOT_BERN_BITS), d_init(ctx, CD_SLOT_INIT), d_table(ctx, CD_SLOT_TABLE);
-    CdBuf d_solver(ctx, CD_SLOT_SOLVER), d_ws(ctx, CD_SLOT_WS);
-    PGX_HIP(d_bits.alloc((size_t)S * pgx_bitmap_stride_words(G) * 8));   // (a view of the loaded table)
+    DevBuf d_bits(ctx, PGX_SLOT_BERN_BITS), d_init(ctx, CD_SLOT_INIT), d_table(ctx, CD_SLOT_TABLE);
+    DevBuf d_solver(ctx, CD_SLOT_SOLVER), d_ws(ctx, CD_SLOT_WS);
+    rc = d_bits.view((size_t)S * pgx_bitmap_stride_words(G) * 8);        // (the loaded table)
+    if (rc != PGX_OK) return rc;
     PGX_HIP(d_init.alloc((size_t)G * 8));
     PGX_HIP(d_table.alloc(cells * 8));
     if (out_solver) PGX_HIP(d_solver.alloc(cells * 8));

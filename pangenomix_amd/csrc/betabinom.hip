@@ -151,12 +151,6 @@ int ks_dev(pgx_ctx *ctx, const uint32_t *d_words, const double *d_draw_cdf, cons
     return PGX_OK;
 }
 
-// device workspace slots (pgx_internal.h) and host staging slots of the two entry points below
-enum { BB_SLOT_WORDS = 110 /* and 111 */, BB_SLOT_CDF = 112, BB_SLOT_MODEL, BB_SLOT_KS, BB_SLOT_HIST, BB_SLOT_IDX };
-enum { BB_HOST_WORDS = 110 /* and 111 */, BB_HOST_IDX = 112 };
-struct BbBuf : DevBuf {
-    BbBuf(pgx_ctx *c, int s) { ctx = c; slot = s; }
-};
 struct Events {
     hipEvent_t e[2] = {nullptr, nullptr};
     ~Events() {
@@ -177,10 +171,10 @@ int ks_host(pgx_ctx *ctx, const double *draw_cdf, const double *model_cdf, uint3
     // a chunk: whole iterations, about chunk_draws draws
     const uint32_t per_chunk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(iterations, chunk_of(chunk_draws) / n_samples));
     const uint64_t chunk_words = 2ull * n_samples * per_chunk;
-    HostVec<uint32_t> h0(ctx, BB_HOST_WORDS, chunk_words), h1(ctx, BB_HOST_WORDS + 1, chunk_words);
+    HostVec<uint32_t> h0(ctx, BB_HOST_WORDS0, chunk_words), h1(ctx, BB_HOST_WORDS1, chunk_words);
     PGX_REQUIRE(h0.ok() && h1.ok(), "cannot allocate page-locked staging buffers");
     uint32_t *hw[2] = {h0.data(), h1.data()};
-    BbBuf dw0(ctx, BB_SLOT_WORDS), dw1(ctx, BB_SLOT_WORDS + 1), d_cdf(ctx, BB_SLOT_CDF), d_model(ctx, BB_SLOT_MODEL),
+    DevBuf dw0(ctx, BB_SLOT_WORDS0), dw1(ctx, BB_SLOT_WORDS1), d_cdf(ctx, BB_SLOT_CDF), d_model(ctx, BB_SLOT_MODEL),
         d_ks(ctx, BB_SLOT_KS), d_hist(ctx, BB_SLOT_HIST);
     const size_t ws = workspace_bytes(L, per_chunk);
     PGX_HIP(dw0.alloc(chunk_words * 4));
@@ -223,10 +217,10 @@ int draws_host(pgx_ctx *ctx, const double *draw_cdf, uint32_t L, uint64_t size, 
     PGX_HIP(hipSetDevice(ctx->device_id));
     hipStream_t stream = ctx->stream;
     const uint64_t per_chunk = std::min(size, chunk_of(chunk_draws));
-    HostVec<uint32_t> hw(ctx, BB_HOST_WORDS, 2 * per_chunk);
+    HostVec<uint32_t> hw(ctx, BB_HOST_WORDS0, 2 * per_chunk);
     HostVec<int64_t> hidx(ctx, BB_HOST_IDX, per_chunk);
     PGX_REQUIRE(hw.ok() && hidx.ok(), "cannot allocate page-locked staging buffers");
-    BbBuf dw(ctx, BB_SLOT_WORDS), d_cdf(ctx, BB_SLOT_CDF), d_idx(ctx, BB_SLOT_IDX);
+    DevBuf dw(ctx, BB_SLOT_WORDS0), d_cdf(ctx, BB_SLOT_CDF), d_idx(ctx, BB_SLOT_IDX);
     PGX_HIP(dw.alloc(per_chunk * 8));
     PGX_HIP(d_cdf.alloc((size_t)L * 8));
     PGX_HIP(d_idx.alloc(per_chunk * 8));

@@ -2364,44 +2364,6 @@ __global__ __launch_bounds__(256) void align_kernel(DevSeqs S, const uint32_t *_
 // ========================================================================================
 namespace {
 
-// Kernels write results straight into these buffers (publish_kernel) and read lists from them, and
-// the host polls for completion instead of making a synchronising call: the memory must be
-// COHERENT (fine-grained, never cached by the GPU), or the device could serve a re-used list from
-// its L2 and leave published records there.
-constexpr unsigned kPinnedFlags = hipHostMallocCoherent | hipHostMallocMapped;
-template <typename T>
-struct Pinned {  // page-locked host staging buffer; bound to a context slot it outlives the call
-    T *p = nullptr;
-    size_t cap = 0;
-    pgx_ctx *ctx = nullptr;
-    int slot = -1;
-    ~Pinned() { if (p && !ctx) (void)hipHostFree(p); }
-    void bind(pgx_ctx *c, int s) { ctx = c; slot = s; }
-    hipError_t reserve(size_t n) {
-        if (n <= cap) return hipSuccess;
-        if (ctx) {
-            if ((int)ctx->host_arena.size() <= slot) ctx->host_arena.resize((size_t)slot + 1, {nullptr, 0});
-            auto &a = ctx->host_arena[(size_t)slot];
-            const size_t bytes = n * sizeof(T);
-            if (!a.first || a.second < bytes) {
-                if (a.first) (void)hipHostFree(a.first);
-                a = {nullptr, 0};
-                const size_t want = bytes + bytes / 2 + 4096;
-                hipError_t e = hipHostMalloc(&a.first, want, kPinnedFlags);
-                if (e != hipSuccess) return e;
-                a.second = want;
-            }
-            p = static_cast<T *>(a.first);
-            cap = a.second / sizeof(T);
-            return hipSuccess;
-        }
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = n + n / 2 + 1024;
-        return hipHostMalloc((void **)&p, cap * sizeof(T), kPinnedFlags);
-    }
-};
-
 enum : uint8_t { ST_OPEN = 0, ST_MEMBER = 1, ST_REP = 2,
                  ST_ABSENT = 3,    // memory-chunked rule: placed by an earlier chunk's sweep, not a member of this window any more
                  ST_NONE = 4 };    // ... a sweep found no representative for it: it stays in the game
@@ -2605,29 +2567,27 @@ static int cluster_greedy_impl(pgx_ctx *ctx, const uint8_t *d_residues, const ui
     // The GPU counts letters, orders the sequences and lays them out; the host sees the lengths as a histogram (one
     // small copy, one synchronisation) and derives its O(longest length) bookkeeping from that. Its per-sequence arrays
     // are filled behind the enqueued device work.
-    DevBuf d_res, d_off, d_len, d_wcode, d_wmult, d_wcnt, d_aa1, d_aas, d_aan, d_lines, d_pool[2], d_idx,
-        d_newbits, d_touched, d_first, d_best_own, d_rcvis, d_counters, d_visits, d_pairsW, d_pairsK, d_blk_list,
-        d_ulist, d_new_list, d_flags, d_gscratch, d_order, d_list, d_gather, d_pk, d_pkoff,
-        d_counters2, d_best2, d_flags2, d_pairsW2, d_gscratch2,   // second set of a window's own state (see `overlap`)
-        d_thr, d_hugewords, d_xsend, d_xrecv,
-        d_hist, d_sortcnt, d_tilesum, d_runs;                     // the prologue's histogram, sort counters, run tables
-    {   // all of them live in the context's workspace (slots 1..)
-        DevBuf *all[] = {&d_res, &d_off, &d_len, &d_wcode, &d_wmult, &d_wcnt, &d_aa1, &d_aas, &d_aan, &d_lines,
-                         &d_pool[0], &d_pool[1], &d_idx, &d_newbits, &d_touched, &d_first, &d_best_own, &d_rcvis,
-                         &d_counters, &d_visits, &d_pairsW, &d_pairsK, &d_blk_list, &d_ulist, &d_new_list, &d_flags,
-                         &d_gscratch, &d_order, &d_list, &d_gather, &d_pk, &d_pkoff,
-                         &d_counters2, &d_best2, &d_flags2, &d_pairsW2, &d_gscratch2, &d_thr, &d_hugewords,
-                         &d_xsend, &d_xrecv, &d_hist, &d_sortcnt, &d_tilesum, &d_runs};
-        int sl = 1;
-        for (DevBuf *b : all) { b->ctx = ctx; b->slot = sl++; }
-    }
+    DevBuf d_res(ctx, CL_SLOT_RES), d_off(ctx, CL_SLOT_OFF), d_len(ctx, CL_SLOT_LEN), d_wcode(ctx, CL_SLOT_WCODE),
+        d_wmult(ctx, CL_SLOT_WMULT), d_wcnt(ctx, CL_SLOT_WCNT), d_aa1(ctx, CL_SLOT_AA1), d_aas(ctx, CL_SLOT_AAS),
+        d_aan(ctx, CL_SLOT_AAN), d_lines(ctx, CL_SLOT_LINES), d_pool[2] = {{ctx, CL_SLOT_POOL0}, {ctx, CL_SLOT_POOL1}},
+        d_idx(ctx, CL_SLOT_IDX), d_newbits(ctx, CL_SLOT_NEWBITS), d_touched(ctx, CL_SLOT_TOUCHED), d_first(ctx, CL_SLOT_FIRST),
+        d_best_own(ctx, CL_SLOT_BEST_OWN), d_rcvis(ctx, CL_SLOT_RCVIS), d_counters(ctx, CL_SLOT_COUNTERS),
+        d_visits(ctx, CL_SLOT_VISITS), d_pairsW(ctx, CL_SLOT_PAIRS_W), d_pairsK(ctx, CL_SLOT_PAIRS_K),
+        d_blk_list(ctx, CL_SLOT_BLK_LIST), d_ulist(ctx, CL_SLOT_ULIST), d_new_list(ctx, CL_SLOT_NEW_LIST),
+        d_flags(ctx, CL_SLOT_FLAGS), d_gscratch(ctx, CL_SLOT_GSCRATCH), d_order(ctx, CL_SLOT_ORDER), d_list(ctx, CL_SLOT_LIST),
+        d_gather(ctx, CL_SLOT_GATHER), d_pk(ctx, CL_SLOT_PK), d_pkoff(ctx, CL_SLOT_PKOFF),
+        // second set of a window's own state (see `overlap`)
+        d_counters2(ctx, CL_SLOT_COUNTERS2), d_best2(ctx, CL_SLOT_BEST2), d_flags2(ctx, CL_SLOT_FLAGS2),
+        d_pairsW2(ctx, CL_SLOT_PAIRS_W2), d_gscratch2(ctx, CL_SLOT_GSCRATCH2),
+        d_thr(ctx, CL_SLOT_THR), d_hugewords(ctx, CL_SLOT_HUGEWORDS), d_xsend(ctx, CL_SLOT_XSEND), d_xrecv(ctx, CL_SLOT_XRECV),
+        // the prologue's histogram, sort counters, run tables
+        d_hist(ctx, CL_SLOT_HIST), d_sortcnt(ctx, CL_SLOT_SORTCNT), d_tilesum(ctx, CL_SLOT_TILESUM), d_runs(ctx, CL_SLOT_RUNS);
     uint32_t n_codes = 1;
     for (int t = 0; t < P->word_len; ++t) n_codes *= nt ? 4u : (uint32_t)kNAA1;
     static_assert(kSegs == 4, "eight codes per word of the round's map");
     const uint32_t bm_words = (n_codes / 8 + 2 + 3) & ~3u;   // words of the round's map of touched codes
     const bool overlap = !nt && !std::getenv("PGX_NO_OVERLAP");   // consecutive windows on two streams, see below
-    DevBuf d_in_len;
-    d_in_len.ctx = ctx; d_in_len.slot = 0;
+    DevBuf d_in_len(ctx, CL_SLOT_IN_LEN);
     PGX_HIP(d_in_len.alloc((size_t)n_in * 4));
     constexpr uint32_t kHistWords = H_BINS + kDevSortMaxLen + 1;
     PGX_HIP(d_hist.alloc((size_t)kHistWords * 4));
@@ -2658,7 +2618,7 @@ static int cluster_greedy_impl(pgx_ctx *ctx, const uint8_t *d_residues, const ui
     }
     LAUNCH_CHECK();
     // (the per-sequence host arrays live in the context's scratch: no allocation, page faults or frees per call)
-    HostVec<uint32_t> h_hist(ctx, 6, kHistWords);
+    HostVec<uint32_t> h_hist(ctx, CL_HOST_HIST, kHistWords);
     PGX_REQUIRE(h_hist.ok(), "out of host memory");
     PGX_HIP(hipMemcpyAsync(h_hist.data(), d_hist.p, (size_t)(H_BINS + kHistLds) * 4, hipMemcpyDeviceToHost, st));
     PGX_HIP(hipStreamSynchronize(st));
@@ -2673,13 +2633,13 @@ static int cluster_greedy_impl(pgx_ctx *ctx, const uint8_t *d_residues, const ui
     phase("  seq_len + histogram + copy");
     const uint32_t *len_hist = h_hist.data() + H_BINS;   // [L] = sequences of L letters that pass min_length
     uint32_t n = 0;
-    HostVec<uint32_t> order(ctx, 1, dev_sort ? 0 : n_in);   // (device sort: bound to n entries below)
+    HostVec<uint32_t> order(ctx, CL_HOST_ORDER, dev_sort ? 0 : n_in);   // (device sort: bound to n entries below)
     std::vector<uint32_t> host_hist;
     if (dev_sort) {
         for (uint32_t L = 0; L <= max_len; ++L) n += len_hist[L];
     } else {
         // a sequence beyond kDevSortMaxLen: the lengths come to the host, which sorts them and uploads the order
-        HostVec<uint32_t> in_len(ctx, 0, n_in);
+        HostVec<uint32_t> in_len(ctx, CL_HOST_IN_LEN, n_in);
         PGX_REQUIRE(in_len.ok() && order.ok(), "out of host memory");
         PGX_HIP(hipMemcpyAsync(in_len.data(), d_in_len.p, (size_t)n_in * 4, hipMemcpyDeviceToHost, st));
         PGX_HIP(hipStreamSynchronize(st));
@@ -2723,19 +2683,19 @@ static int cluster_greedy_impl(pgx_ctx *ctx, const uint8_t *d_residues, const ui
     PGX_REQUIRE(n < (1u << 30), "too many sequences for the index entries (30 bits)");
     uint32_t mshift = 8;                         // smallest field that holds n (and the strike-out value above it)
     while ((1u << mshift) <= n) ++mshift;
-    if (dev_sort) order = HostVec<uint32_t>(ctx, 1, n);   // (arrives behind the device's sort, read when outputs are written)
+    if (dev_sort) order = HostVec<uint32_t>(ctx, CL_HOST_ORDER, n);   // (arrives behind the device's sort, read when outputs are written)
 
     // sequences n .. 2n-1 are the reverse complements (nucleotides, both strands)
     const uint32_t nv = both ? 2 * n : n;
-    HostVec<uint64_t> h_off(ctx, 2, (size_t)nv + 1);
-    HostVec<uint32_t> h_len(ctx, 3, nv);
+    HostVec<uint64_t> h_off(ctx, CL_HOST_OFF, (size_t)nv + 1);
+    HostVec<uint32_t> h_len(ctx, CL_HOST_LEN, nv);
     PGX_REQUIRE(order.ok() && h_off.ok() && h_len.ok(), "out of host memory");
     // The sorted list is one run of equal lengths per histogram bucket: run r holds the sequences of max_len - r
     // letters. Its first sorted position, residue offset and packed-word offset are prefix sums over the buckets; inside
     // a run offsets advance by the length. The device (layout_kernel) and the host (below, behind the enqueued work)
     // expand the same tables.
     const uint32_t n_runs = max_len + 1;
-    HostVec<uint64_t> h_runs(ctx, 7, 2 * ((size_t)n_runs + 1));
+    HostVec<uint64_t> h_runs(ctx, CL_HOST_RUNS, 2 * ((size_t)n_runs + 1));
     PGX_REQUIRE(h_runs.ok(), "out of host memory");
     uint64_t *const run_off = h_runs.data();
     uint32_t *const run_pos = reinterpret_cast<uint32_t *>(run_off + n_runs + 1), *const run_pk = run_pos + n_runs + 1;
@@ -2755,7 +2715,7 @@ static int cluster_greedy_impl(pgx_ctx *ctx, const uint8_t *d_residues, const ui
     // per-query thresholds in double, exactly as the sequential rule computes them
     // They depend on the length only: one small table per threshold (host, in double), expanded per sequence on
     // the device (thresholds_kernel) instead of three host passes and three uploads of n integers.
-    HostVec<int32_t> h_thr(ctx, 5, 3 * ((size_t)max_len + 1));
+    HostVec<int32_t> h_thr(ctx, CL_HOST_THR, 3 * ((size_t)max_len + 1));
     PGX_REQUIRE(h_thr.ok(), "out of host memory");
     {
         int32_t *t_aa1 = h_thr.data(), *t_aas = t_aa1 + max_len + 1, *t_aan = t_aas + max_len + 1;
@@ -2981,7 +2941,7 @@ static int cluster_greedy_impl(pgx_ctx *ctx, const uint8_t *d_residues, const ui
     DevSeqs DS{d_res.as<uint8_t>(), d_off.as<uint64_t>(), d_len.as<uint32_t>(),
                d_wcode.as<uint32_t>(), d_wmult.as<uint16_t>(), d_wcnt.as<uint32_t>(),
                d_pk.as<uint32_t>(), d_pkoff.as<uint32_t>(), n, nt ? 4 : kNAA1, nt ? 4 : 2, nt ? 1 : 0, mshift};
-    HostVec<uint32_t> h_wcnt(ctx, 8, n);
+    HostVec<uint32_t> h_wcnt(ctx, CL_HOST_WCNT, n);
     PGX_REQUIRE(h_wcnt.ok(), "out of host memory");
     PGX_HIP(hipMemcpyAsync(h_wcnt.data(), d_wcnt.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
 
@@ -3017,25 +2977,23 @@ static int cluster_greedy_impl(pgx_ctx *ctx, const uint8_t *d_residues, const ui
     PGX_HIP(d_first.alloc((size_t)tag_stride * n_codes * 4 + 16));
     // ---- windows --------------------------------------------------------------------------
     std::vector<uint32_t> rep_seq;            // representative index -> sorted sequence index
-    HostVec<int32_t> cluster_of(ctx, 9, n, -1);   // sorted sequence index -> cluster
-    HostVec<int32_t> iden_of(ctx, 10, n, -1);     // identical residues against the representative, -1 = is one
+    HostVec<int32_t> cluster_of(ctx, CL_HOST_CLUSTER_OF, n, -1);   // sorted sequence index -> cluster
+    HostVec<int32_t> iden_of(ctx, CL_HOST_IDEN_OF, n, -1);     // identical residues against the representative, -1 = is one
     PGX_REQUIRE(cluster_of.ok() && iden_of.ok(), "out of host memory");
-    Pinned<Pair> hW, hK;
-    Pinned<unsigned long long> h_best, h_rcvis;
-    Pinned<uint32_t> h_cnt, h_blk, h_new, h_list, h_push;
-    Pinned<Pair> h_gather;
-    hW.bind(ctx, 0); hK.bind(ctx, 1); h_best.bind(ctx, 2); h_cnt.bind(ctx, 3); h_blk.bind(ctx, 4);
-    h_new.bind(ctx, 5); h_rcvis.bind(ctx, 6); h_list.bind(ctx, 7); h_gather.bind(ctx, 8); h_push.bind(ctx, 9);
+    Pinned<Pair> hW(ctx, CL_PIN_W), hK(ctx, CL_PIN_K);
+    Pinned<unsigned long long> h_best(ctx, CL_PIN_BEST), h_rcvis(ctx, CL_PIN_RCVIS);
+    Pinned<uint32_t> h_cnt(ctx, CL_PIN_CNT), h_blk(ctx, CL_PIN_BLK), h_new(ctx, CL_PIN_NEW), h_list(ctx, CL_PIN_LIST),
+        h_push(ctx, CL_PIN_PUSH);
+    Pinned<Pair> h_gather(ctx, CL_PIN_GATHER);
     constexpr uint32_t kPrefix = 65536;  // initial capacity (records) of the host copy of the window's pairs
     PGX_HIP(h_best.reserve(window_cap)); PGX_HIP(h_cnt.reserve(C_COUNT)); PGX_HIP(h_blk.reserve(kBlockCap));
     PGX_HIP(h_new.reserve(window_cap)); PGX_HIP(hK.reserve(pair_cap_k)); PGX_HIP(hW.reserve(kPrefix));
     PGX_HIP(h_rcvis.reserve(window_cap)); PGX_HIP(h_push.reserve(2 * (size_t)window_cap + 4 * kBlockCap));
     PGX_HIP(h_list.reserve(pair_cap_k)); PGX_HIP(h_gather.reserve(pair_cap_k));
     // what a window's CLOSE publishes has its own host buffers, one set per window in flight
-    Pinned<Pair> hW2;
-    Pinned<unsigned long long> h_best2;
-    Pinned<uint32_t> h_ccnt, h_ccnt2;
-    hW2.bind(ctx, 10); h_best2.bind(ctx, 11); h_ccnt.bind(ctx, 12); h_ccnt2.bind(ctx, 13);
+    Pinned<Pair> hW2(ctx, CL_PIN_W2);
+    Pinned<unsigned long long> h_best2(ctx, CL_PIN_BEST2);
+    Pinned<uint32_t> h_ccnt(ctx, CL_PIN_CCNT), h_ccnt2(ctx, CL_PIN_CCNT2);
     PGX_HIP(h_ccnt.reserve(C_COUNT));
     if (overlap) { PGX_HIP(hW2.reserve(kPrefix)); PGX_HIP(h_best2.reserve(window_cap)); PGX_HIP(h_ccnt2.reserve(C_COUNT)); }
     struct Events {   // (destroyed on every way out)
@@ -3071,7 +3029,7 @@ static int cluster_greedy_impl(pgx_ctx *ctx, const uint8_t *d_residues, const ui
     unsigned long long *const d_best_set[2] = {d_best, exchanging ? d_best + PGX_EXCHANGE_WORDS : d_best2.as<unsigned long long>()};
     uint8_t *const d_flags_set[2] = {d_flags.as<uint8_t>(), d_flags2.as<uint8_t>()};
     std::vector<uint8_t> status(window_cap);
-    HostVec<uint8_t> strand_of(ctx, 11, n, (uint8_t)0);
+    HostVec<uint8_t> strand_of(ctx, CL_HOST_STRAND_OF, n, (uint8_t)0);
     PGX_REQUIRE(strand_of.ok(), "out of host memory");
     std::vector<unsigned long long> winner_key(window_cap);  // strand<<63 | minc<<32 | sequence index of the winner
     std::vector<uint32_t> new_reps, order_k, rank_of(window_cap), bucket_k(kBlockCap + 2), fill_k(kBlockCap + 2), flight;
@@ -3115,8 +3073,7 @@ static int cluster_greedy_impl(pgx_ctx *ctx, const uint8_t *d_residues, const ui
     // Memory-chunked rule: at a flush position every sequence not yet placed is compared with the index as it is
     // (a SWEEP: windows over the rest of the list that run phase A only; a member with an accepted representative is
     // placed there and then, the others stay in the game), then the index is emptied and clustering goes on.
-    Pinned<uint8_t> h_taken;        // per sorted sequence: placed by a sweep (the device reads it through the mapping)
-    h_taken.bind(ctx, 14);
+    Pinned<uint8_t> h_taken(ctx, CL_PIN_TAKEN);   // per sorted sequence: placed by a sweep (the device reads it through the mapping)
     if (!flush_at.empty()) { PGX_HIP(h_taken.reserve(n)); std::fill(h_taken.p, h_taken.p + n, (uint8_t)0); }
     auto drain = [&]() -> int {     // nothing in flight, no bookkeeping pending
         if (deferred) { int rc = deferred(); deferred = nullptr; if (rc) return rc; }
@@ -3746,9 +3703,7 @@ extern "C" int pgx_cluster_greedy(pgx_ctx *ctx, const uint8_t *residues, const u
     PGX_HIP(hipSetDevice(ctx->device_id));
     for (uint32_t i = 0; i < n_in; ++i) PGX_REQUIRE(offsets[i + 1] >= offsets[i], "offsets must be non-decreasing");
     const uint64_t total_in = n_in ? offsets[n_in] : 0;
-    DevBuf d_res, d_off;
-    d_res.ctx = ctx; d_res.slot = 70;      // the upload buffers live in the context's workspace too
-    d_off.ctx = ctx; d_off.slot = 71;
+    DevBuf d_res(ctx, CL_SLOT_UP_RES), d_off(ctx, CL_SLOT_UP_OFF);   // the upload buffers live in the context's workspace too
     PGX_HIP(d_res.alloc(total_in + 16));
     PGX_HIP(d_off.alloc(((size_t)n_in + 1) * 8));
     if (n_in) {

@@ -322,13 +322,6 @@ int dict_match_dev(pgx_ctx *ctx, const uint8_t *d_keys, const u64 *d_key_offsets
     return PGX_OK;
 }
 
-// device buffers of the host-pointer entries (slots after bernoulli_cd's): the loaded set stays in the first three
-enum { DM_SLOT_KEYS = 190, DM_SLOT_KEY_OFF, DM_SLOT_TABLE, DM_SLOT_QUERIES, DM_SLOT_QUERY_OFF, DM_SLOT_OUT,
-       SD_SLOT_ROWS, SD_SLOT_GENOMES, SD_SLOT_A_BITS, SD_SLOT_A_CNT, SD_SLOT_B_BITS, SD_SLOT_B_CNT, SD_SLOT_OUT };
-struct DmBuf : DevBuf {
-    DmBuf(pgx_ctx *c, int s) { ctx = c; slot = s; }
-};
-
 // offsets of a host entry: n + 1 entries that never decrease, below 2^32
 int host_offsets_ok(const uint64_t *offsets, uint32_t n) {
     for (uint32_t i = 0; i < n; ++i) PGX_REQUIRE(offsets[i] <= offsets[i + 1], "offsets must not decrease");
@@ -336,7 +329,7 @@ int host_offsets_ok(const uint64_t *offsets, uint32_t n) {
     return PGX_OK;
 }
 
-int upload_strings(pgx_ctx *ctx, DmBuf &d_blob, DmBuf &d_off, const uint8_t *blob, const uint64_t *offsets, uint32_t n) {
+int upload_strings(pgx_ctx *ctx, DevBuf &d_blob, DevBuf &d_off, const uint8_t *blob, const uint64_t *offsets, uint32_t n) {
     const size_t bytes = (size_t)offsets[n];
     PGX_HIP(d_blob.alloc(bytes));
     PGX_HIP(d_off.alloc(((size_t)n + 1) * 8));
@@ -358,7 +351,7 @@ int dict_load_host(pgx_ctx *ctx, const uint8_t *keys, const uint64_t *key_offset
     PGX_REQUIRE(key_offsets[n_keys] == 0 || keys, "NULL keys");
     PGX_HIP(hipSetDevice(ctx->device_id));
     ctx->dict_loaded = false;
-    DmBuf d_keys(ctx, DM_SLOT_KEYS), d_off(ctx, DM_SLOT_KEY_OFF), d_table(ctx, DM_SLOT_TABLE), d_out(ctx, DM_SLOT_OUT);
+    DevBuf d_keys(ctx, DM_SLOT_KEYS), d_off(ctx, DM_SLOT_KEY_OFF), d_table(ctx, DM_SLOT_TABLE), d_out(ctx, DM_SLOT_OUT);
     rc = upload_strings(ctx, d_keys, d_off, keys, key_offsets, n_keys);
     if (rc != PGX_OK) return rc;
     PGX_HIP(d_table.alloc((size_t)dict_slots(n_keys) * 8));
@@ -398,7 +391,7 @@ int dict_query_host(pgx_ctx *ctx, const uint8_t *queries, const uint64_t *query_
     // the loaded set: the pointers pgx_dict_load left in the context (its slots are touched by nothing else)
     const uint8_t *d_keys = static_cast<const uint8_t *>(ctx->dict_d_keys);
     const u64 *d_off = static_cast<const u64 *>(ctx->dict_d_offsets), *d_table = static_cast<const u64 *>(ctx->dict_d_table);
-    DmBuf d_q(ctx, DM_SLOT_QUERIES), d_qoff(ctx, DM_SLOT_QUERY_OFF), d_out(ctx, DM_SLOT_OUT);
+    DevBuf d_q(ctx, DM_SLOT_QUERIES), d_qoff(ctx, DM_SLOT_QUERY_OFF), d_out(ctx, DM_SLOT_OUT);
     rc = upload_strings(ctx, d_q, d_qoff, queries, query_offsets, n_queries);
     if (rc != PGX_OK) return rc;
     PGX_HIP(d_out.alloc((size_t)n_queries * 4));
@@ -434,8 +427,8 @@ int sets_diff_host(pgx_ctx *ctx, const int32_t *a_rows, const int32_t *a_genomes
     if (n_genomes == 0) return PGX_OK;
     PGX_REQUIRE(out_a_only && out_b_only, "NULL argument");
     PGX_HIP(hipSetDevice(ctx->device_id));
-    DmBuf d_a(ctx, SD_SLOT_A_BITS), d_acnt(ctx, SD_SLOT_A_CNT), d_b(ctx, SD_SLOT_B_BITS), d_bcnt(ctx, SD_SLOT_B_CNT);
-    DmBuf d_out(ctx, SD_SLOT_OUT);
+    DevBuf d_a(ctx, SD_SLOT_A_BITS), d_acnt(ctx, SD_SLOT_A_CNT), d_b(ctx, SD_SLOT_B_BITS), d_bcnt(ctx, SD_SLOT_B_CNT);
+    DevBuf d_out(ctx, SD_SLOT_OUT);
     int rc = pgx_upload_and_build_bitmap(ctx, a_rows, a_genomes, n_a, n_rows, n_genomes, SD_SLOT_ROWS, SD_SLOT_GENOMES, d_a,
                                          d_acnt);
     if (rc == PGX_OK) rc = pgx_read_record_counters(ctx, d_acnt, nullptr);   // (an index out of range fails here)

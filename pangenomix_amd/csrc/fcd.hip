@@ -45,18 +45,17 @@ FcdGeom make_geom(uint32_t n_rows, uint32_t n_genomes) {
     g.stride = pgx_bitmap_stride_words(n_rows);
     g.lanes = g.stride / 2;                              // (stride is a multiple of 16 words)
     g.chunks = ceil_div_u32(g.lanes, FC_CHUNK);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    g.off_u = take((size_t)n_genomes * g.stride * 8);
-    g.off_acc = take((size_t)g.stride * 8);
-    g.off_w = take((size_t)g.stride * 64 * 4);           // one counter per bit of a column, pad bits included
-    g.off_raw = take((size_t)n_genomes * 8);
-    g.off_live = take((size_t)n_genomes * 4);
-    g.off_colcnt = take((size_t)n_genomes * 8);
-    g.off_cols = take((size_t)n_genomes * 4);
-    g.off_rows = take((size_t)n_rows * 4);
-    g.off_res = take(sizeof(FcdResult));
-    g.bytes = off;
+    WsLayout ws;
+    g.off_u = ws.take((size_t)n_genomes * g.stride * 8);
+    g.off_acc = ws.take((size_t)g.stride * 8);
+    g.off_w = ws.take((size_t)g.stride * 64 * 4);        // one counter per bit of a column, pad bits included
+    g.off_raw = ws.take((size_t)n_genomes * 8);
+    g.off_live = ws.take((size_t)n_genomes * 4);
+    g.off_colcnt = ws.take((size_t)n_genomes * 8);
+    g.off_cols = ws.take((size_t)n_genomes * 4);
+    g.off_rows = ws.take((size_t)n_rows * 4);
+    g.off_res = ws.take(sizeof(FcdResult));
+    g.bytes = ws.off;
     return g;
 }
 
@@ -272,35 +271,6 @@ __global__ __launch_bounds__(FC_THREADS) void fcd_rows_to_mask_kernel(const int3
     }
 }
 
-// the table from the pipeline's resident bitmap: row i, column j of the output = row row_map[i], column col_map[j] of
-// the input (col_map NULL: the same column). One thread per output word.
-__global__ __launch_bounds__(FC_THREADS) void fcd_gather_kernel(const unsigned long long *__restrict__ src, uint32_t src_stride,
-                                                                const int32_t *__restrict__ row_map,
-                                                                const int32_t *__restrict__ col_map, uint32_t G, uint32_t S,
-                                                                uint32_t stride, unsigned long long *__restrict__ dst) {
-    const uint64_t total = (uint64_t)S * stride;
-    for (uint64_t idx = (uint64_t)blockIdx.x * FC_THREADS + threadIdx.x; idx < total; idx += (uint64_t)gridDim.x * FC_THREADS) {
-        const uint32_t s = (uint32_t)(idx / stride), wd = (uint32_t)(idx % stride);
-        const unsigned long long *row = src + (size_t)(col_map ? (uint32_t)col_map[s] : s) * src_stride;
-        unsigned long long word = 0;
-        for (uint32_t b = 0; b < 64; ++b) {
-            const uint32_t i = wd * 64 + b;
-            if (i >= G) break;
-            const uint32_t m = (uint32_t)row_map[i];
-            word |= ((row[m >> 6] >> (m & 63u)) & 1ull) << b;
-        }
-        dst[idx] = word;
-    }
-}
-
-// device buffers of the host-pointer entry points (slots after the beta-binomial test's); host scratch slot 120
-enum { FC_SLOT_BITS = 120, FC_SLOT_ROWS, FC_SLOT_GENOMES, FC_SLOT_CNT, FC_SLOT_WS, FC_SLOT_MAP, FC_SLOT_CMAP, FC_SLOT_CROWS,
-       FC_SLOT_CCOLS, FC_SLOT_CLEARED };
-constexpr int FC_HOST_RES = 120;
-struct FcBuf : DevBuf {
-    FcBuf(pgx_ctx *c, int s) { ctx = c; slot = s; }
-};
-
 struct FcdWs {
     FcdGeom g;
     unsigned long long *U, *acc, *raw, *colcnt;
@@ -469,10 +439,9 @@ int fcd_host(pgx_ctx *ctx, const int32_t *rows, const int32_t *genomes, uint64_t
     PGX_HIP(hipSetDevice(ctx->device_id));
     memset(info, 0, sizeof(*info));
     fcd_reset_result(ctx);
-    FcBuf d_bits(ctx, FC_SLOT_BITS), d_cnt(ctx, FC_SLOT_CNT), d_ws(ctx, FC_SLOT_WS);
-    int rc = pgx_upload_and_build_bitmap(ctx, rows, genomes, n_records, n_rows, S, FC_SLOT_ROWS, FC_SLOT_GENOMES, d_bits, d_cnt);
+    DevBuf d_bits(ctx, FC_SLOT_BITS), d_cnt(ctx, FC_SLOT_CNT), d_ws(ctx, FC_SLOT_WS);
     uint64_t dup = 0;
-    if (rc == PGX_OK) rc = pgx_read_record_counters(ctx, d_cnt, &dup);
+    const int rc = pgx_load_coo_bitmap(ctx, rows, genomes, n_records, n_rows, S, FC_SLOT_ROWS, FC_SLOT_GENOMES, d_bits, d_cnt, &dup);
     if (rc != PGX_OK) return rc;
     if (out_duplicates) *out_duplicates = dup;
     if (dup) return PGX_OK;                   // not a 0/1 table: nothing is decomposed
@@ -485,34 +454,14 @@ int fcd_resident(pgx_ctx *ctx, uint64_t token, const int32_t *row_map, const int
                  uint64_t limit, uint32_t flags, const double *dim_factors, pgx_fcd_info_t *info) {
     PGX_REQUIRE(ctx && info, "NULL argument");
     PGX_REQUIRE(G == 0 || row_map, "NULL row map");
-    PGX_REQUIRE(token != 0 && token == ctx->resident_token && S == ctx->resident_genomes,
-                "the bitmap of that token is not resident any more");
+    ResidentBitmap src;
+    int rc = pgx_resident_bitmap(ctx, token, S, &src);
+    if (rc != PGX_OK) return rc;
     PGX_REQUIRE((uint64_t)G < (1ull << 31), "table too large");
-    for (uint32_t i = 0; i < G; ++i)
-        PGX_REQUIRE(row_map[i] >= 0 && (uint32_t)row_map[i] < ctx->resident_genes, "row map entry out of range");
-    for (uint32_t j = 0; col_map && j < S; ++j)
-        PGX_REQUIRE(col_map[j] >= 0 && (uint32_t)col_map[j] < S, "column map entry out of range");
     PGX_HIP(hipSetDevice(ctx->device_id));
-    const uint32_t stride = pgx_bitmap_stride_words(G);
-    const uint32_t src_stride = pgx_bitmap_stride_words(ctx->resident_genes);
-    FcBuf d_src(ctx, PGX_SLOT_RESIDENT), d_map(ctx, FC_SLOT_MAP), d_cmap(ctx, FC_SLOT_CMAP), d_bits(ctx, FC_SLOT_BITS),
-        d_ws(ctx, FC_SLOT_WS);
-    PGX_HIP(d_src.alloc((size_t)S * src_stride * 8));       // (a view of the resident slot: no allocation)
-    PGX_HIP(d_map.alloc((size_t)G * 4));
-    PGX_HIP(d_cmap.alloc((size_t)S * 4));
-    PGX_HIP(d_bits.alloc((size_t)S * stride * 8));
-    if (G) PGX_HIP(hipMemcpyAsync(d_map.p, row_map, (size_t)G * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (col_map && S) PGX_HIP(hipMemcpyAsync(d_cmap.p, col_map, (size_t)S * 4, hipMemcpyHostToDevice, ctx->stream));
-    const uint64_t total = (uint64_t)S * stride;
-    if (total) {
-        const uint64_t want = (total + FC_THREADS - 1) / FC_THREADS;
-        ProfScope prof(ctx, "fcd_gather_kernel", ctx->stream);
-        fcd_gather_kernel<<<(uint32_t)(want < 8192 ? want : 8192), FC_THREADS, 0, ctx->stream>>>(
-            d_src.as<unsigned long long>(), src_stride, d_map.as<int32_t>(), col_map ? d_cmap.as<int32_t>() : nullptr, G, S,
-            stride, d_bits.as<unsigned long long>());
-        PGX_HIP(hipGetLastError());
-    }
-    PGX_HIP(hipStreamSynchronize(ctx->stream));             // (the maps are the caller's: read before the call returns)
+    DevBuf d_map(ctx, FC_SLOT_MAP), d_cmap(ctx, FC_SLOT_CMAP), d_bits(ctx, FC_SLOT_BITS), d_ws(ctx, FC_SLOT_WS);
+    rc = pgx_gather_resident(ctx, src, row_map, col_map, G, S, d_map, &d_cmap, d_bits, "fcd_gather_kernel");
+    if (rc != PGX_OK) return rc;
     const size_t nws = make_geom(G, S).bytes;
     PGX_HIP(d_ws.alloc(nws));
     return fcd_run(ctx, d_bits.as<uint64_t>(), G, S, limit, flags, dim_factors, d_ws.p, nws, ctx->stream, info);
@@ -559,11 +508,10 @@ int fcd_coverage(pgx_ctx *ctx, const int32_t *rows, const int32_t *genomes, uint
     }
     PGX_HIP(hipSetDevice(ctx->device_id));
     *out_ones = 0;
-    FcBuf d_bits(ctx, FC_SLOT_BITS), d_cnt(ctx, FC_SLOT_CNT), d_ws(ctx, FC_SLOT_WS), d_crows(ctx, FC_SLOT_CROWS),
+    DevBuf d_bits(ctx, FC_SLOT_BITS), d_cnt(ctx, FC_SLOT_CNT), d_ws(ctx, FC_SLOT_WS), d_crows(ctx, FC_SLOT_CROWS),
         d_ccols(ctx, FC_SLOT_CCOLS), d_cleared(ctx, FC_SLOT_CLEARED);
-    int rc = pgx_upload_and_build_bitmap(ctx, rows, genomes, n_records, n_rows, S, FC_SLOT_ROWS, FC_SLOT_GENOMES, d_bits, d_cnt);
     uint64_t dup = 0;
-    if (rc == PGX_OK) rc = pgx_read_record_counters(ctx, d_cnt, &dup);
+    int rc = pgx_load_coo_bitmap(ctx, rows, genomes, n_records, n_rows, S, FC_SLOT_ROWS, FC_SLOT_GENOMES, d_bits, d_cnt, &dup);
     if (rc != PGX_OK) return rc;
     if (out_duplicates) *out_duplicates = dup;
     if (dup || n_rows == 0 || S == 0) {

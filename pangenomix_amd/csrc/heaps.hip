@@ -91,8 +91,6 @@ __global__ __launch_bounds__(256) void heaps_fit_kernel(const T *__restrict__ pa
     if (lane == 0) { alpha[it] = a; kappa[it] = k; if (steps) steps[it] = n; }
 }
 
-enum { HP_SLOT_TAB = 96, HP_SLOT_A, HP_SLOT_K };   // (after pancore's 80-94: 90 is the resident bitmap)
-
 }  // namespace
 
 extern "C" {
@@ -117,9 +115,7 @@ int pgx_heaps_fit(pgx_ctx *ctx, const double *pan, uint32_t n_iter, uint32_t n_g
     if (n_iter == 0) return PGX_OK;
     PGX_REQUIRE(pan && out_alpha && out_kappa && n_genomes > 0, "NULL argument");
     PGX_HIP(hipSetDevice(ctx->device_id));
-    DevBuf d_tab, d_a, d_k;
-    d_tab.ctx = d_a.ctx = d_k.ctx = ctx;
-    d_tab.slot = HP_SLOT_TAB; d_a.slot = HP_SLOT_A; d_k.slot = HP_SLOT_K;
+    DevBuf d_tab(ctx, HP_SLOT_TAB), d_a(ctx, HP_SLOT_A), d_k(ctx, HP_SLOT_K);
     const size_t nb = (size_t)n_iter * n_genomes * 8;
     PGX_HIP(d_tab.alloc(nb));
     PGX_HIP(d_a.alloc((size_t)n_iter * 8));

@@ -290,14 +290,26 @@ __global__ __launch_bounds__(256) void row_counts_kernel(const unsigned long lon
     counts[r] = c;
 }
 
-// K3 device buffers of the host-pointer entry points live in the context's grow-only workspace
-// (slots after the clustering's), so repeated calls neither allocate nor free.
-enum { PC_SLOT_ROWS = 80, PC_SLOT_GENOMES, PC_SLOT_BITS, PC_SLOT_PERMS, PC_SLOT_PAN, PC_SLOT_CORE, PC_SLOT_WS, PC_SLOT_CNT, PC_SLOT_COUNTS, PC_SLOT_TABLE, PC_SLOT_RESIDENT, PC_SLOT_RES_A, PC_SLOT_RES_B, PC_SLOT_RES_C, PC_SLOT_RES_D };
-static_assert(PC_SLOT_RESIDENT == PGX_SLOT_RESIDENT, "pgx_internal.h names the resident slot");
-static_assert(PC_SLOT_RES_D < 96, "pancore's slots end before the Heaps fit's");
-struct PcBuf : DevBuf {
-    PcBuf(pgx_ctx *c, int s) { ctx = c; slot = s; }
-};
+// the table from the pipeline's resident bitmap: row i, column j of the output = row row_map[i], column col_map[j] of
+// the input (col_map NULL: the same column). One thread per output word.
+__global__ __launch_bounds__(256) void resident_gather_kernel(const unsigned long long *__restrict__ src, uint32_t src_stride,
+                                                              const int32_t *__restrict__ row_map,
+                                                              const int32_t *__restrict__ col_map, uint32_t G, uint32_t S,
+                                                              uint32_t stride, unsigned long long *__restrict__ dst) {
+    const uint64_t total = (uint64_t)S * stride;
+    for (uint64_t idx = (uint64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (uint64_t)gridDim.x * 256) {
+        const uint32_t s = (uint32_t)(idx / stride), wd = (uint32_t)(idx % stride);
+        const unsigned long long *row = src + (size_t)(col_map ? (uint32_t)col_map[s] : s) * src_stride;
+        unsigned long long word = 0;
+        for (uint32_t b = 0; b < 64; ++b) {
+            const uint32_t i = wd * 64 + b;
+            if (i >= G) break;
+            const uint32_t m = (uint32_t)row_map[i];
+            word |= ((row[m >> 6] >> (m & 63u)) & 1ull) << b;
+        }
+        dst[idx] = word;
+    }
+}
 
 // Host threads that run beside an entry point's own work: whatever was started is joined at the end of the scope on
 // every way out of it, an exception from starting a further thread included (destroying a joinable std::thread is
@@ -311,10 +323,10 @@ struct JoinedThreads {
 
 // ---- shared with bernoulli.hip (pgx_internal.h) -------------------------------------------------------------------
 int pgx_upload_and_build_bitmap(pgx_ctx *ctx, const int32_t *rows, const int32_t *genomes, uint64_t n_records,
-                                uint32_t n_rows, uint32_t n_genomes, int slot_rows, int slot_genomes, DevBuf &d_bits,
+                                uint32_t n_rows, uint32_t n_genomes, DevSlot slot_rows, DevSlot slot_genomes, DevBuf &d_bits,
                                 DevBuf &d_cnt) {
     const size_t nbits = (size_t)n_genomes * pgx_bitmap_stride_words(n_rows) * 8;
-    PcBuf d_rows(ctx, slot_rows), d_genomes(ctx, slot_genomes);
+    DevBuf d_rows(ctx, slot_rows), d_genomes(ctx, slot_genomes);
     PGX_HIP(d_rows.alloc(n_records * 4));
     PGX_HIP(d_genomes.alloc(n_records * 4));
     PGX_HIP(d_bits.alloc(nbits));
@@ -334,6 +346,51 @@ int pgx_read_record_counters(pgx_ctx *ctx, DevBuf &d_cnt, uint64_t *out_duplicat
     PGX_HIP(hipStreamSynchronize(ctx->stream));
     PGX_REQUIRE(cnt[1] == 0, "record with row or genome index out of range");
     if (out_duplicates) *out_duplicates = cnt[0];
+    return PGX_OK;
+}
+
+int pgx_load_coo_bitmap(pgx_ctx *ctx, const int32_t *rows, const int32_t *genomes, uint64_t n_records, uint32_t n_rows,
+                        uint32_t n_genomes, DevSlot slot_rows, DevSlot slot_genomes, DevBuf &d_bits, DevBuf &d_cnt,
+                        uint64_t *duplicates) {
+    int rc = pgx_upload_and_build_bitmap(ctx, rows, genomes, n_records, n_rows, n_genomes, slot_rows, slot_genomes, d_bits, d_cnt);
+    if (rc == PGX_OK) rc = pgx_read_record_counters(ctx, d_cnt, duplicates);
+    return rc;
+}
+
+int pgx_resident_bitmap(pgx_ctx *ctx, uint64_t token, uint32_t n_genomes, ResidentBitmap *out) {
+    PGX_REQUIRE(token != 0 && token == ctx->resident_token && n_genomes == ctx->resident_genomes,
+                "the bitmap of that token is not resident any more");
+    out->n_genes = ctx->resident_genes;
+    out->stride = pgx_bitmap_stride_words(ctx->resident_genes);
+    DevBuf d_src(ctx, PGX_SLOT_RESIDENT);
+    const int rc = d_src.view((size_t)n_genomes * out->stride * 8);
+    out->d_bits = d_src.as<uint64_t>();
+    return rc;
+}
+
+int pgx_gather_resident(pgx_ctx *ctx, const ResidentBitmap &src, const int32_t *row_map, const int32_t *col_map,
+                        uint32_t G, uint32_t S, DevBuf &d_map, DevBuf *d_cmap, DevBuf &d_bits,
+                        const char *prof_name) {
+    for (uint32_t i = 0; i < G; ++i)
+        PGX_REQUIRE(row_map[i] >= 0 && (uint32_t)row_map[i] < src.n_genes, "row map entry out of range");
+    for (uint32_t j = 0; col_map && j < S; ++j)
+        PGX_REQUIRE(col_map[j] >= 0 && (uint32_t)col_map[j] < S, "column map entry out of range");
+    const uint32_t stride = pgx_bitmap_stride_words(G);
+    PGX_HIP(d_map.alloc((size_t)G * 4));
+    if (d_cmap) PGX_HIP(d_cmap->alloc((size_t)S * 4));
+    PGX_HIP(d_bits.alloc((size_t)S * stride * 8));
+    if (G) PGX_HIP(hipMemcpyAsync(d_map.p, row_map, (size_t)G * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (col_map && S) PGX_HIP(hipMemcpyAsync(d_cmap->p, col_map, (size_t)S * 4, hipMemcpyHostToDevice, ctx->stream));
+    const uint64_t total = (uint64_t)S * stride;
+    if (total) {
+        const uint64_t want = (total + 255) / 256;
+        ProfScope prof(ctx, prof_name, ctx->stream);
+        resident_gather_kernel<<<(uint32_t)(want < 8192 ? want : 8192), 256, 0, ctx->stream>>>(
+            (const unsigned long long *)src.d_bits, src.stride, d_map.as<int32_t>(), col_map ? d_cmap->as<int32_t>() : nullptr, G, S,
+            stride, d_bits.as<unsigned long long>());
+        PGX_HIP(hipGetLastError());
+    }
+    PGX_HIP(hipStreamSynchronize(ctx->stream));             // (the maps are the caller's: read before the call returns)
     return PGX_OK;
 }
 
@@ -382,7 +439,7 @@ int pgx_presence_bitmap(pgx_ctx *ctx, const int32_t *rows, const int32_t *genome
     PGX_REQUIRE(n_records == 0 || (rows && genomes), "NULL record arrays");
     PGX_HIP(hipSetDevice(ctx->device_id));
     const size_t nbits = (size_t)n_genomes * pgx_bitmap_stride_words(n_rows) * 8;
-    PcBuf d_bits(ctx, PC_SLOT_BITS), d_cnt(ctx, PC_SLOT_CNT);
+    DevBuf d_bits(ctx, PC_SLOT_BITS), d_cnt(ctx, PC_SLOT_CNT);
     int rc = pgx_upload_and_build_bitmap(ctx, rows, genomes, n_records, n_rows, n_genomes, PC_SLOT_ROWS, PC_SLOT_GENOMES,
                                          d_bits, d_cnt);
     if (rc != PGX_OK) return rc;
@@ -440,7 +497,7 @@ static int pan_core_from_device_bitmap(pgx_ctx *ctx, const uint64_t *d_bits, uin
         PGX_REQUIRE((uint32_t)perms[k] < n_genomes, "permutation entry out of range");
     const size_t nperm = (size_t)n_iter * n_genomes * 4;
     const size_t nws = pgx_pan_core_workspace_bytes(n_genes, n_genomes, n_iter);
-    PcBuf d_perms(ctx, PC_SLOT_PERMS), d_pan(ctx, PC_SLOT_PAN), d_core(ctx, PC_SLOT_CORE), d_ws(ctx, PC_SLOT_WS);
+    DevBuf d_perms(ctx, PC_SLOT_PERMS), d_pan(ctx, PC_SLOT_PAN), d_core(ctx, PC_SLOT_CORE), d_ws(ctx, PC_SLOT_WS);
     PGX_HIP(d_perms.alloc(nperm));
     PGX_HIP(d_pan.alloc(nperm));
     PGX_HIP(d_core.alloc(nperm));
@@ -461,7 +518,7 @@ int pgx_pan_core(pgx_ctx *ctx, const uint64_t *bits, uint32_t n_genes, uint32_t 
     PGX_REQUIRE(bits && perms && out_pan && out_core, "NULL argument");
     PGX_HIP(hipSetDevice(ctx->device_id));
     const size_t nbits = (size_t)n_genomes * pgx_bitmap_stride_words(n_genes) * 8;
-    PcBuf d_bits(ctx, PC_SLOT_BITS);
+    DevBuf d_bits(ctx, PC_SLOT_BITS);
     PGX_HIP(d_bits.alloc(nbits));
     PGX_HIP(hipMemcpyAsync(d_bits.p, bits, nbits, hipMemcpyHostToDevice, ctx->stream));
     int rc = pan_core_from_device_bitmap(ctx, d_bits.as<uint64_t>(), n_genes, n_genomes, perms, n_iter, out_pan, out_core);
@@ -477,7 +534,7 @@ int pgx_pan_core_coo(pgx_ctx *ctx, const int32_t *rows, const int32_t *genomes, 
     PGX_REQUIRE(n_records == 0 || (rows && genomes), "NULL record arrays");
     PGX_REQUIRE(n_iter == 0 || n_genomes == 0 || (perms && out_pan && out_core), "NULL argument");
     PGX_HIP(hipSetDevice(ctx->device_id));
-    PcBuf d_bits(ctx, PC_SLOT_BITS), d_cnt(ctx, PC_SLOT_CNT);
+    DevBuf d_bits(ctx, PC_SLOT_BITS), d_cnt(ctx, PC_SLOT_CNT);
     int rc = pgx_upload_and_build_bitmap(ctx, rows, genomes, n_records, n_genes, n_genomes, PC_SLOT_ROWS, PC_SLOT_GENOMES,
                                          d_bits, d_cnt);
     if (rc != PGX_OK) return rc;
@@ -495,7 +552,7 @@ static int table_from_device_bitmap(pgx_ctx *ctx, const uint64_t *d_bits, uint32
                                     const int32_t *perms, uint32_t n_iter, double *out_table) {
     const size_t nperm = (size_t)n_iter * n_genomes * 4;
     const size_t nws = pgx_pan_core_workspace_bytes(n_genes, n_genomes, n_iter);
-    PcBuf d_perms(ctx, PC_SLOT_PERMS), d_ws(ctx, PC_SLOT_WS), d_table(ctx, PC_SLOT_TABLE);
+    DevBuf d_perms(ctx, PC_SLOT_PERMS), d_ws(ctx, PC_SLOT_WS), d_table(ctx, PC_SLOT_TABLE);
     PGX_HIP(d_perms.alloc(nperm));
     PGX_HIP(d_ws.alloc(nws));
     PGX_HIP(d_table.alloc(nperm * 4));
@@ -531,7 +588,7 @@ int pgx_pan_core_table(pgx_ctx *ctx, const int32_t *rows, const int32_t *genomes
     char draw_error[512] = "";
     uint64_t bad[4] = {0, 0, 0, 0};
     const unsigned T = !(values && n_records) ? 0u : n_records < (1u << 20) ? 1u : 4u;
-    PcBuf d_bits(ctx, PC_SLOT_BITS), d_cnt(ctx, PC_SLOT_CNT);
+    DevBuf d_bits(ctx, PC_SLOT_BITS), d_cnt(ctx, PC_SLOT_CNT);
     int rc;
     {
         JoinedThreads threads;
@@ -576,7 +633,7 @@ int pgx_bitmap_from_clusters(pgx_ctx *ctx, const int32_t *cluster_of_group, uint
     ctx->resident_token = 0;                         // (whatever was resident is gone from here on)
     const uint32_t stride = pgx_bitmap_stride_words(n_genes);
     const size_t nbits = (size_t)n_genomes * stride * 8;
-    PcBuf d_bits(ctx, PC_SLOT_RESIDENT), d_cl(ctx, PC_SLOT_RES_A), d_grp(ctx, PC_SLOT_RES_B), d_file(ctx, PC_SLOT_RES_C),
+    DevBuf d_bits(ctx, PGX_SLOT_RESIDENT), d_cl(ctx, PC_SLOT_RES_A), d_grp(ctx, PC_SLOT_RES_B), d_file(ctx, PC_SLOT_RES_C),
         d_gof(ctx, PC_SLOT_RES_D), d_cnt(ctx, PC_SLOT_CNT);
     PGX_HIP(d_bits.alloc(nbits));
     PGX_HIP(d_cl.alloc(n_groups * 4));
@@ -613,12 +670,12 @@ int pgx_bitmap_from_clusters(pgx_ctx *ctx, const int32_t *cluster_of_group, uint
 
 int pgx_bitmap_resident_read(pgx_ctx *ctx, uint64_t token, uint64_t *out_bits) try {
     PGX_REQUIRE(ctx && out_bits, "NULL argument");
-    PGX_REQUIRE(token != 0 && token == ctx->resident_token, "the bitmap of that token is not resident any more");
+    ResidentBitmap res;
+    const int rc = pgx_resident_bitmap(ctx, token, ctx->resident_genomes, &res);
+    if (rc != PGX_OK) return rc;
     PGX_HIP(hipSetDevice(ctx->device_id));
-    PcBuf d_bits(ctx, PC_SLOT_RESIDENT);
-    const size_t nbits = (size_t)ctx->resident_genomes * pgx_bitmap_stride_words(ctx->resident_genes) * 8;
-    PGX_HIP(d_bits.alloc(nbits));                     // (a view of the slot: no allocation)
-    PGX_HIP(hipMemcpyAsync(out_bits, d_bits.p, nbits, hipMemcpyDeviceToHost, ctx->stream));
+    const size_t nbits = (size_t)ctx->resident_genomes * res.stride * 8;
+    PGX_HIP(hipMemcpyAsync(out_bits, res.d_bits, nbits, hipMemcpyDeviceToHost, ctx->stream));
     PGX_HIP(hipStreamSynchronize(ctx->stream));
     return PGX_OK;
 } catch (...) { return guarded_catch(__func__); }
@@ -626,16 +683,16 @@ int pgx_bitmap_resident_read(pgx_ctx *ctx, uint64_t token, uint64_t *out_bits) t
 int pgx_pan_core_table_resident(pgx_ctx *ctx, uint64_t token, uint32_t n_genes, uint32_t n_genomes, uint32_t *mt_key,
                                 int32_t *mt_pos, uint32_t n_iter, int32_t *out_perms, double *out_table) try {
     PGX_REQUIRE(ctx && mt_key && mt_pos, "NULL argument");
-    PGX_REQUIRE(token != 0 && token == ctx->resident_token && n_genes == ctx->resident_genes && n_genomes == ctx->resident_genomes,
-                "the bitmap of that token is not resident any more");
+    ResidentBitmap res;
+    int rc = pgx_resident_bitmap(ctx, token, n_genomes, &res);
+    if (rc != PGX_OK) return rc;
+    PGX_REQUIRE(n_genes == res.n_genes, "the bitmap of that token is not resident any more");
     PGX_REQUIRE(n_iter == 0 || n_genomes == 0 || (out_perms && out_table), "NULL argument");
     PGX_HIP(hipSetDevice(ctx->device_id));
-    int rc = pgx_legacy_shuffles(mt_key, mt_pos, n_genomes, n_iter, out_perms);
+    rc = pgx_legacy_shuffles(mt_key, mt_pos, n_genomes, n_iter, out_perms);
     if (rc != PGX_OK) return rc;
     if (n_iter == 0 || n_genomes == 0) return PGX_OK;
-    PcBuf d_bits(ctx, PC_SLOT_RESIDENT);
-    PGX_HIP(d_bits.alloc((size_t)n_genomes * pgx_bitmap_stride_words(n_genes) * 8));   // (a view of the slot)
-    rc = table_from_device_bitmap(ctx, d_bits.as<uint64_t>(), n_genes, n_genomes, out_perms, n_iter, out_table);
+    rc = table_from_device_bitmap(ctx, res.d_bits, n_genes, n_genomes, out_perms, n_iter, out_table);
     if (rc != PGX_OK) return rc;
     PGX_HIP(hipStreamSynchronize(ctx->stream));
     return PGX_OK;
@@ -662,7 +719,7 @@ int pgx_row_counts(pgx_ctx *ctx, const int32_t *rows, const int32_t *genomes, ui
     PGX_REQUIRE(n_records == 0 || (rows && genomes), "NULL record arrays");
     PGX_REQUIRE(n_rows == 0 || out_counts, "NULL argument");
     PGX_HIP(hipSetDevice(ctx->device_id));
-    PcBuf d_bits(ctx, PC_SLOT_BITS), d_cnt(ctx, PC_SLOT_CNT), d_counts(ctx, PC_SLOT_COUNTS);
+    DevBuf d_bits(ctx, PC_SLOT_BITS), d_cnt(ctx, PC_SLOT_CNT), d_counts(ctx, PC_SLOT_COUNTS);
     int rc = pgx_upload_and_build_bitmap(ctx, rows, genomes, n_records, n_rows, n_genomes, PC_SLOT_ROWS, PC_SLOT_GENOMES,
                                          d_bits, d_cnt);
     if (rc != PGX_OK) return rc;

@@ -61,11 +61,10 @@ static void prof_resolve(pgx_ctx *ctx) {
 
 int pgx_staged_h2d(pgx_ctx *ctx, void *dst, const void *src, size_t bytes, hipStream_t stream) {
     constexpr size_t kChunk = 4u << 20;
-    constexpr int kStageSlot = 30;           // host scratch slot of the staging buffers
     const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
     const unsigned T = (unsigned)std::min<size_t>(std::min(4u, std::max(1u, hw / 2)), bytes / (2 * kChunk));
     if (T < 2) { PGX_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream)); return PGX_OK; }
-    HostVec<uint8_t> stage(ctx, kStageSlot, (size_t)T * 2 * kChunk);
+    HostVec<uint8_t> stage(ctx, PGX_HOST_STAGE, (size_t)T * 2 * kChunk);
     if (!stage.ok() || !stage.data()) { PGX_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream)); return PGX_OK; }
     while (ctx->stage_events.size() < 2 * (size_t)T) {
         hipEvent_t e = nullptr;

@@ -23,6 +23,63 @@ struct ProfSlot {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
 };
 
+// Every buffer a context keeps between calls lives in one of three grow-only tables, and every slot of a table has ONE
+// name, here: two users of one slot silently overwrite (or reallocate) each other's data. To add a buffer, add an
+// enumerator to its module's group; DevBuf, HostVec and Pinned take nothing but these types.
+enum DevSlot : int {        // pgx_ctx::arena, through DevBuf
+    // cluster.hip: pgx_cluster_greedy_dev, then the two upload buffers of pgx_cluster_greedy
+    CL_SLOT_IN_LEN = 0, CL_SLOT_RES, CL_SLOT_OFF, CL_SLOT_LEN, CL_SLOT_WCODE, CL_SLOT_WMULT, CL_SLOT_WCNT, CL_SLOT_AA1,
+    CL_SLOT_AAS, CL_SLOT_AAN, CL_SLOT_LINES, CL_SLOT_POOL0, CL_SLOT_POOL1, CL_SLOT_IDX, CL_SLOT_NEWBITS, CL_SLOT_TOUCHED,
+    CL_SLOT_FIRST, CL_SLOT_BEST_OWN, CL_SLOT_RCVIS, CL_SLOT_COUNTERS, CL_SLOT_VISITS, CL_SLOT_PAIRS_W, CL_SLOT_PAIRS_K,
+    CL_SLOT_BLK_LIST, CL_SLOT_ULIST, CL_SLOT_NEW_LIST, CL_SLOT_FLAGS, CL_SLOT_GSCRATCH, CL_SLOT_ORDER, CL_SLOT_LIST,
+    CL_SLOT_GATHER, CL_SLOT_PK, CL_SLOT_PKOFF, CL_SLOT_COUNTERS2, CL_SLOT_BEST2, CL_SLOT_FLAGS2, CL_SLOT_PAIRS_W2,
+    CL_SLOT_GSCRATCH2, CL_SLOT_THR, CL_SLOT_HUGEWORDS, CL_SLOT_XSEND, CL_SLOT_XRECV, CL_SLOT_HIST, CL_SLOT_SORTCNT,
+    CL_SLOT_TILESUM, CL_SLOT_RUNS, CL_SLOT_UP_RES, CL_SLOT_UP_OFF,
+    // pancore.hip; PGX_SLOT_RESIDENT is the pipeline's resident bitmap (pgx_resident_bitmap)
+    PC_SLOT_ROWS, PC_SLOT_GENOMES, PC_SLOT_BITS, PC_SLOT_PERMS, PC_SLOT_PAN, PC_SLOT_CORE, PC_SLOT_WS, PC_SLOT_CNT,
+    PC_SLOT_COUNTS, PC_SLOT_TABLE, PGX_SLOT_RESIDENT, PC_SLOT_RES_A, PC_SLOT_RES_B, PC_SLOT_RES_C, PC_SLOT_RES_D,
+    // heaps.hip
+    HP_SLOT_TAB, HP_SLOT_A, HP_SLOT_K,
+    // bernoulli.hip; PGX_SLOT_BERN_BITS is the table pgx_bernoulli_load* left, read in place by bernoulli_cd.hip
+    PGX_SLOT_BERN_BITS, BN_SLOT_ROWS, BN_SLOT_GENOMES, BN_SLOT_CNT, BN_SLOT_MAP, BN_SLOT_PQ, BN_SLOT_OUT, BN_SLOT_WS,
+    // betabinom.hip
+    BB_SLOT_WORDS0, BB_SLOT_WORDS1, BB_SLOT_CDF, BB_SLOT_MODEL, BB_SLOT_KS, BB_SLOT_HIST, BB_SLOT_IDX,
+    // fcd.hip
+    FC_SLOT_BITS, FC_SLOT_ROWS, FC_SLOT_GENOMES, FC_SLOT_CNT, FC_SLOT_WS, FC_SLOT_MAP, FC_SLOT_CMAP, FC_SLOT_CROWS,
+    FC_SLOT_CCOLS, FC_SLOT_CLEARED,
+    // assoc.hip
+    AS_SLOT_BITS, AS_SLOT_ROWS, AS_SLOT_GENOMES, AS_SLOT_CNT, AS_SLOT_WS, AS_SLOT_RMAP, AS_SLOT_CMAP, AS_SLOT_MASKS,
+    AS_SLOT_TP, AS_SLOT_INC, AS_SLOT_BLOCK, AS_SLOT_REP,
+    // runs.hip
+    RN_SLOT_ABITS, RN_SLOT_AROWS, RN_SLOT_AGENOMES, RN_SLOT_ACNT, RN_SLOT_GBITS, RN_SLOT_GROWS, RN_SLOT_GGENOMES,
+    RN_SLOT_GCNT, RN_SLOT_WS, RN_SLOT_START, RN_SLOT_GENE, RN_SLOT_DERIVED, RN_SLOT_DIFF, RN_SLOT_PER_GENOME,
+    RN_SLOT_PER_RUN, RN_SLOT_TOTAL, RN_SLOT_BEST, RN_SLOT_BEST_COUNT,
+    // scan.hip
+    SC_SLOT_TEXT, SC_SLOT_KEYS, SC_SLOT_FOUND, SC_SLOT_WS,
+    // bernoulli_cd.hip
+    CD_SLOT_INIT, CD_SLOT_TABLE, CD_SLOT_SOLVER, CD_SLOT_WS,
+    // dict.hip: the loaded set stays in the first three; then pgx_genome_sets_diff
+    DM_SLOT_KEYS, DM_SLOT_KEY_OFF, DM_SLOT_TABLE, DM_SLOT_QUERIES, DM_SLOT_QUERY_OFF, DM_SLOT_OUT,
+    SD_SLOT_ROWS, SD_SLOT_GENOMES, SD_SLOT_A_BITS, SD_SLOT_A_CNT, SD_SLOT_B_BITS, SD_SLOT_B_CNT, SD_SLOT_OUT,
+    DEV_SLOT_COUNT
+};
+enum HostSlot : int {       // pgx_ctx::host_scratch, through HostVec
+    // cluster.hip
+    CL_HOST_IN_LEN = 0, CL_HOST_ORDER, CL_HOST_OFF, CL_HOST_LEN, CL_HOST_THR, CL_HOST_HIST, CL_HOST_RUNS, CL_HOST_WCNT,
+    CL_HOST_CLUSTER_OF, CL_HOST_IDEN_OF, CL_HOST_STRAND_OF,
+    PGX_HOST_STAGE,         // pgx_core.hip: the staging buffers of pgx_staged_h2d
+    BB_HOST_WORDS0, BB_HOST_WORDS1, BB_HOST_IDX,
+    FC_HOST_RES,
+    AS_HOST_STATUS,
+    RN_HOST_STATUS,
+    HOST_SLOT_COUNT
+};
+enum PinSlot : int {        // pgx_ctx::host_arena, through Pinned (cluster.hip)
+    CL_PIN_W = 0, CL_PIN_K, CL_PIN_BEST, CL_PIN_CNT, CL_PIN_BLK, CL_PIN_NEW, CL_PIN_RCVIS, CL_PIN_LIST, CL_PIN_GATHER,
+    CL_PIN_PUSH, CL_PIN_W2, CL_PIN_BEST2, CL_PIN_CCNT, CL_PIN_CCNT2, CL_PIN_TAKEN,
+    PIN_SLOT_COUNT
+};
+
 struct pgx_ctx {
     int device_id;
     hipStream_t stream;  // used by the host-pointer entry points
@@ -33,13 +90,13 @@ struct pgx_ctx {
     std::vector<ProfSlot> prof;
     std::vector<hipEvent_t> event_pool;
     // grow-only device workspace, reused by successive calls on this context (slot -> buffer)
-    std::vector<std::pair<void *, size_t>> arena;
-    // grow-only page-locked host staging buffers (slot -> buffer), same idea
-    std::vector<std::pair<void *, size_t>> host_arena;
+    std::pair<void *, size_t> arena[DEV_SLOT_COUNT] = {};
+    // grow-only coherent page-locked host buffers (slot -> buffer), same idea
+    std::pair<void *, size_t> host_arena[PIN_SLOT_COUNT] = {};
     // grow-only page-locked host scratch (slot -> buffer): the per-sequence arrays of a clustering call
     // (tens of MB) are neither allocated, faulted in nor freed again by every call, and their copies to
     // and from the device are asynchronous (from pageable memory every hipMemcpyAsync blocked the host)
-    std::vector<std::pair<void *, size_t>> host_scratch;
+    std::pair<void *, size_t> host_scratch[HOST_SLOT_COUNT] = {};
     std::vector<hipEvent_t> stage_events;   // pgx_staged_h2d: one per staging buffer (its last DMA)
     // the gene x genome bitmap a pipeline left on the device (pgx_bitmap_from_clusters): its token, shape, buffer
     uint64_t resident_token = 0, resident_next = 1;
@@ -69,8 +126,8 @@ template <typename T>
 struct HostVec {
     T *p = nullptr;
     size_t n = 0;
-    HostVec(pgx_ctx *ctx, int slot, size_t count) { bind(ctx, slot, count); }
-    HostVec(pgx_ctx *ctx, int slot, size_t count, T fill) {
+    HostVec(pgx_ctx *ctx, HostSlot slot, size_t count) { bind(ctx, slot, count); }
+    HostVec(pgx_ctx *ctx, HostSlot slot, size_t count, T fill) {
         bind(ctx, slot, count);
         if (p) std::fill(p, p + n, fill);
     }
@@ -84,9 +141,8 @@ struct HostVec {
     T *end() { return p + n; }
 
 private:
-    void bind(pgx_ctx *ctx, int slot, size_t count) {
-        if ((int)ctx->host_scratch.size() <= slot) ctx->host_scratch.resize((size_t)slot + 1, {nullptr, 0});
-        auto &a = ctx->host_scratch[(size_t)slot];
+    void bind(pgx_ctx *ctx, HostSlot slot, size_t count) {
+        auto &a = ctx->host_scratch[slot];
         const size_t bytes = count * sizeof(T) + 64;
         if (a.second < bytes) {
             if (a.first) (void)hipHostFree(a.first);
@@ -99,6 +155,36 @@ private:
         p = static_cast<T *>(a.first);
         n = p ? count : 0;
         if (!p && count) n = count;  // ok() reports the failure
+    }
+};
+
+// Kernels write results straight into these buffers (publish_kernel) and read lists from them, and
+// the host polls for completion instead of making a synchronising call: the memory must be
+// COHERENT (fine-grained, never cached by the GPU), or the device could serve a re-used list from
+// its L2 and leave published records there.
+constexpr unsigned kPinnedFlags = hipHostMallocCoherent | hipHostMallocMapped;
+template <typename T>
+struct Pinned {  // page-locked host staging buffer in a context slot: it outlives the call
+    T *p = nullptr;
+    size_t cap = 0;
+    pgx_ctx *ctx;
+    PinSlot slot;
+    Pinned(pgx_ctx *c, PinSlot s) : ctx(c), slot(s) {}
+    hipError_t reserve(size_t n) {
+        if (n <= cap) return hipSuccess;
+        auto &a = ctx->host_arena[slot];
+        const size_t bytes = n * sizeof(T);
+        if (!a.first || a.second < bytes) {
+            if (a.first) (void)hipHostFree(a.first);
+            a = {nullptr, 0};
+            const size_t want = bytes + bytes / 2 + 4096;
+            hipError_t e = hipHostMalloc(&a.first, want, kPinnedFlags);
+            if (e != hipSuccess) return e;
+            a.second = want;
+        }
+        p = static_cast<T *>(a.first);
+        cap = a.second / sizeof(T);
+        return hipSuccess;
     }
 };
 
@@ -130,21 +216,16 @@ struct ProfScope {
         }                                                                                  \
     } while (0)
 
-// Device buffer. Stand-alone (freed on scope exit) or, when bound to a context slot, a view
-// of that slot of the context's grow-only workspace: repeated calls then neither allocate
-// nor free (hipFree of GB-sized buffers stalls the queue for milliseconds).
+// Device buffer: a view of one slot of the context's grow-only workspace, so that repeated calls neither
+// allocate nor free (hipFree of GB-sized buffers stalls the queue for milliseconds).
 struct DevBuf {
     void *p = nullptr;
-    pgx_ctx *ctx = nullptr;
-    int slot = -1;
-    ~DevBuf() {
-        if (p && !ctx) (void)hipFree(p);
-    }
+    pgx_ctx *ctx;
+    DevSlot slot;
+    DevBuf(pgx_ctx *c, DevSlot s) : ctx(c), slot(s) {}
     hipError_t alloc(size_t bytes) {
         if (!bytes) bytes = 16;
-        if (!ctx) return hipMalloc(&p, bytes);
-        if ((int)ctx->arena.size() <= slot) ctx->arena.resize((size_t)slot + 1, {nullptr, 0});
-        auto &a = ctx->arena[(size_t)slot];
+        auto &a = ctx->arena[slot];
         if (!a.first || a.second < bytes) {
             if (a.first) (void)hipFree(a.first);
             a = {nullptr, 0};
@@ -156,18 +237,32 @@ struct DevBuf {
         p = a.first;
         return hipSuccess;
     }
+    // The slot as an earlier call filled it (state the context keeps): never allocates or frees, and fails when the
+    // slot does not hold `bytes`.
+    int view(size_t bytes) {
+        const auto &a = ctx->arena[slot];
+        if (!a.first || a.second < bytes) {
+            pgx_set_error("workspace slot %d holds %zu bytes where %zu were kept", (int)slot, a.first ? a.second : (size_t)0, bytes);
+            return PGX_ERR_INTERNAL;
+        }
+        p = a.first;
+        return PGX_OK;
+    }
     template <typename T>
     T *as() {
         return static_cast<T *>(p);
     }
 };
 
-// Workspace slot of the pipeline's resident bitmap (pancore.hip), read in place by bernoulli.hip. Slots in use:
-// pancore 80-94, heaps 96-98, bernoulli 100-107, betabinom 110-116 (host staging slots 110-112), fcd 120-129 (host scratch slot 120),
-// assoc 130-141 (host scratch slot 130), runs 150-167 (host scratch slot 150), scan 170-173, bernoulli_cd 180-183, dict 190-202.
-constexpr int PGX_SLOT_RESIDENT = 90;
-// Workspace slot of the table loaded by pgx_bernoulli_load* (bernoulli.hip), read in place by bernoulli_cd.hip.
-constexpr int PGX_SLOT_BERN_BITS = 100;
+// Layout of a workspace in one allocation: every part starts at a multiple of 256 bytes.
+struct WsLayout {
+    size_t off = 0;
+    size_t take(size_t bytes) {
+        const size_t o = off;
+        off += (bytes + 255) & ~(size_t)255;
+        return o;
+    }
+};
 
 static inline uint32_t ceil_div_u32(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
 
@@ -183,11 +278,30 @@ int pgx_staged_h2d(pgx_ctx *ctx, void *dst, const void *src, size_t bytes, hipSt
 // through the workspace slots slot_rows / slot_genomes; d_bits and d_cnt are the caller's (bound to slots of its own,
 // so that one user's table is not overwritten by another's call). d_cnt: 2 x u64, see presence_bitmap_kernel.
 int pgx_upload_and_build_bitmap(pgx_ctx *ctx, const int32_t *rows, const int32_t *genomes, uint64_t n_records,
-                                uint32_t n_rows, uint32_t n_genomes, int slot_rows, int slot_genomes, DevBuf &d_bits,
+                                uint32_t n_rows, uint32_t n_genomes, DevSlot slot_rows, DevSlot slot_genomes, DevBuf &d_bits,
                                 DevBuf &d_cnt);
 // Its counterpart: the two counters back, ctx->stream synchronised; fails when a record was out of range (none of
 // those was written), stores the number of duplicate coordinates through out_duplicates unless that is NULL.
 int pgx_read_record_counters(pgx_ctx *ctx, DevBuf &d_cnt, uint64_t *out_duplicates);
+// The two in one call, for a caller that enqueues nothing in between: the table is in d_bits, *duplicates set unless NULL.
+int pgx_load_coo_bitmap(pgx_ctx *ctx, const int32_t *rows, const int32_t *genomes, uint64_t n_records, uint32_t n_rows,
+                        uint32_t n_genomes, DevSlot slot_rows, DevSlot slot_genomes, DevBuf &d_bits, DevBuf &d_cnt,
+                        uint64_t *duplicates);
+
+// The bitmap pgx_bitmap_from_clusters left in the context (pancore.hip): n_genomes x stride words, n_genes rows.
+struct ResidentBitmap {
+    const uint64_t *d_bits;
+    uint32_t n_genes, stride;
+};
+// Fails unless `token` names the bitmap that is resident and that has n_genomes genomes; the slot is only viewed.
+int pgx_resident_bitmap(pgx_ctx *ctx, uint64_t token, uint32_t n_genomes, ResidentBitmap *out);
+// d_bits = the table of G rows x S genomes gathered from it: row i, column j = row row_map[i], column col_map[j] of the
+// resident bitmap (col_map NULL: the same column). The maps (host) are checked before anything else (PGX_ERR_INVALID:
+// nothing was touched), then uploaded into d_map / d_cmap (NULL for a caller that never has a column map); ctx->stream is
+// synchronised, so they are the caller's again on return. prof_name: the kernel's name in the profile.
+int pgx_gather_resident(pgx_ctx *ctx, const ResidentBitmap &src, const int32_t *row_map, const int32_t *col_map,
+                        uint32_t G, uint32_t S, DevBuf &d_map, DevBuf *d_cmap, DevBuf &d_bits,
+                        const char *prof_name);
 
 // all-gather of `count` uint64 per process with the context's RCCL communicator, enqueued on `stream` (rccl_exchange.hip)
 int pgx_rccl_all_gather_u64(pgx_ctx *ctx, const void *send, void *recv, size_t count, hipStream_t stream);

@@ -40,12 +40,11 @@ RunsGeom make_geom(uint32_t n_alleles, uint32_t n_runs, uint32_t n_genomes) {
     RunsGeom g;
     g.a_stride = pgx_bitmap_stride_words(n_alleles);
     g.o_stride = pgx_bitmap_stride_words(n_runs);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    g.off_diff = take((size_t)n_genomes * g.o_stride * 8);
-    g.off_counts = take((size_t)n_alleles * 4);
-    g.off_status = take(16);
-    g.bytes = off;
+    WsLayout ws;
+    g.off_diff = ws.take((size_t)n_genomes * g.o_stride * 8);
+    g.off_counts = ws.take((size_t)n_alleles * 4);
+    g.off_status = ws.take(16);
+    g.bytes = ws.off;
     return g;
 }
 
@@ -181,7 +180,7 @@ int runs_run(pgx_ctx *ctx, const uint64_t *d_abits, uint32_t n_alleles, const ui
     const RunsGeom g = make_geom(n_alleles, n_runs, n_genomes);
     PGX_REQUIRE(d_ws && ws_bytes >= g.bytes, "workspace too small (see pgx_allele_runs_workspace_bytes)");
     PGX_REQUIRE(((uintptr_t)d_ws & 15u) == 0, "workspace must be 16-byte aligned");
-    HostVec<uint32_t> h_status(ctx, 150, 4);
+    HostVec<uint32_t> h_status(ctx, RN_HOST_STATUS, 4);
     if (!h_status.ok()) { pgx_set_error("%s: out of page-locked host memory", __func__); return PGX_ERR_NOMEM; }
     char *p = (char *)d_ws;
     uint32_t *status = (uint32_t *)(p + g.off_status);
@@ -232,14 +231,6 @@ int runs_run(pgx_ctx *ctx, const uint64_t *d_abits, uint32_t n_alleles, const ui
     return PGX_OK;
 }
 
-// device buffers of the host-pointer entry (slots after assoc's); host scratch slot 150
-enum { RN_SLOT_ABITS = 150, RN_SLOT_AROWS, RN_SLOT_AGENOMES, RN_SLOT_ACNT, RN_SLOT_GBITS, RN_SLOT_GROWS, RN_SLOT_GGENOMES,
-       RN_SLOT_GCNT, RN_SLOT_WS, RN_SLOT_START, RN_SLOT_GENE, RN_SLOT_DERIVED, RN_SLOT_DIFF, RN_SLOT_PER_GENOME,
-       RN_SLOT_PER_RUN, RN_SLOT_TOTAL, RN_SLOT_BEST, RN_SLOT_BEST_COUNT };
-struct RnBuf : DevBuf {
-    RnBuf(pgx_ctx *c, int s) { ctx = c; slot = s; }
-};
-
 int runs_host(pgx_ctx *ctx, const int32_t *a_rows, const int32_t *a_genomes, uint64_t a_records, uint32_t n_alleles,
               const int32_t *g_rows, const int32_t *g_genomes, uint64_t g_records, uint32_t n_genes, uint32_t n_genomes,
               const uint32_t *run_start, uint32_t n_runs, const int32_t *gene_of_run, const RunsOut &out,
@@ -259,7 +250,7 @@ int runs_host(pgx_ctx *ctx, const int32_t *a_rows, const int32_t *a_genomes, uin
     if (out_duplicates) out_duplicates[0] = out_duplicates[1] = 0;
     PGX_HIP(hipSetDevice(ctx->device_id));
     hipStream_t stream = ctx->stream;
-    RnBuf d_abits(ctx, RN_SLOT_ABITS), d_acnt(ctx, RN_SLOT_ACNT), d_gbits(ctx, RN_SLOT_GBITS), d_gcnt(ctx, RN_SLOT_GCNT);
+    DevBuf d_abits(ctx, RN_SLOT_ABITS), d_acnt(ctx, RN_SLOT_ACNT), d_gbits(ctx, RN_SLOT_GBITS), d_gcnt(ctx, RN_SLOT_GCNT);
     uint64_t dup[2] = {0, 0};
     rc = pgx_upload_and_build_bitmap(ctx, a_rows, a_genomes, a_records, n_alleles, n_genomes, RN_SLOT_AROWS, RN_SLOT_AGENOMES,
                                      d_abits, d_acnt);
@@ -274,7 +265,7 @@ int runs_host(pgx_ctx *ctx, const int32_t *a_rows, const int32_t *a_genomes, uin
 
     const RunsGeom g = make_geom(n_alleles, n_runs, n_genomes);
     const size_t out_bytes = (size_t)n_genomes * g.o_stride * 8;
-    RnBuf d_ws(ctx, RN_SLOT_WS), d_start(ctx, RN_SLOT_START), d_gene(ctx, RN_SLOT_GENE), d_derived(ctx, RN_SLOT_DERIVED),
+    DevBuf d_ws(ctx, RN_SLOT_WS), d_start(ctx, RN_SLOT_START), d_gene(ctx, RN_SLOT_GENE), d_derived(ctx, RN_SLOT_DERIVED),
         d_diff(ctx, RN_SLOT_DIFF), d_per_genome(ctx, RN_SLOT_PER_GENOME), d_per_run(ctx, RN_SLOT_PER_RUN),
         d_total(ctx, RN_SLOT_TOTAL), d_best(ctx, RN_SLOT_BEST), d_best_count(ctx, RN_SLOT_BEST_COUNT);
     PGX_HIP(d_ws.alloc(g.bytes));

@@ -199,12 +199,6 @@ int scan_run(pgx_ctx *ctx, const uint8_t *d_text, uint64_t text_bytes, const uin
     return PGX_OK;
 }
 
-// device buffers of the host-pointer entry (slots after runs')
-enum { SC_SLOT_TEXT = 170, SC_SLOT_KEYS, SC_SLOT_FOUND, SC_SLOT_WS };
-struct ScBuf : DevBuf {
-    ScBuf(pgx_ctx *c, int s) { ctx = c; slot = s; }
-};
-
 int scan_host(pgx_ctx *ctx, const uint8_t *text, uint64_t text_bytes, const uint8_t *keys, uint32_t n_keys, uint32_t window,
               uint32_t flags, uint8_t *out_found) {
     int rc = scan_args(ctx, text, text_bytes, keys, n_keys, window, flags, out_found);
@@ -215,7 +209,7 @@ int scan_host(pgx_ctx *ctx, const uint8_t *text, uint64_t text_bytes, const uint
     hipStream_t stream = ctx->stream;
     const ScanGeom g = make_geom(n_keys);
     const size_t key_bytes = (size_t)n_keys * window;
-    ScBuf d_text(ctx, SC_SLOT_TEXT), d_keys(ctx, SC_SLOT_KEYS), d_found(ctx, SC_SLOT_FOUND), d_ws(ctx, SC_SLOT_WS);
+    DevBuf d_text(ctx, SC_SLOT_TEXT), d_keys(ctx, SC_SLOT_KEYS), d_found(ctx, SC_SLOT_FOUND), d_ws(ctx, SC_SLOT_WS);
     PGX_HIP(d_text.alloc((size_t)text_bytes));
     PGX_HIP(d_keys.alloc(key_bytes));
     PGX_HIP(d_found.alloc(n_keys));
