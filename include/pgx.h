@@ -20,6 +20,8 @@
  *                                       and the per-iteration eCDF loop -> pgx_bbn_*
  *   fcd.py:15-138, :199-219             formal_concept_decomposition() / compute_concept_coverage(): the dense
  *                                       np.ix_ block sums -> pgx_fcd*
+ *   fcd.py:168-196                      compute_concept_list_similarity(): the Python double loop over pairs of
+ *                                       sets -> pgx_fcd_match*
  *   sparse_utils.py:73-109, ml_pipelines.py:349-388   compress_rows_spmatrix() / contingency_tables_from_sparse(): the
  *                                       per-phenotype association screen -> pgx_assoc*
  *   pangenome.py:1246-1330, :1812-1889  validate_gene_table[_dense]() / extract_dominant_alleles(): the Python loops
@@ -506,7 +508,27 @@ int pgx_bbn_draws(pgx_ctx *ctx, const double *draw_cdf, uint32_t sim_limit, uint
  * A concept that clears nothing (the reference would loop for ever) fails with PGX_ERR_INTERNAL.
  *   pgx_fcd_coverage   out_cleared[i] = the ones concept i clears when the given concepts (layout as pgx_fcd_fetch's; no
  *                      column twice in one concept) are cleared from the table one after the other with the same kernel;
- *                      out_ones = the ones of the table. */
+ *                      out_ones = the ones of the table.
+ *
+ * Comparing two concept lists (compute_concept_list_similarity, reference fcd.py:168-196). A concept is a SET of rows and
+ * a set of columns (an index listed twice counts once); O[i][j] = |rows1[i] & rows2[j]| * |cols1[i] & cols2[j]| are the
+ * cells concept i of F1 and concept j of F2 share. For i = 0 .. k, k = min(n1, n2): concept i takes the unmatched j with
+ * the largest O[i][j], the lowest j among equals (an overlap of 0 still takes one); match[i] = j, overlap[i] = O[i][j],
+ * total = their sum. The matrix is formed 256 concepts of F1 at a time and never as a whole, unless the caller asks for
+ * it: out_matrix / d_matrix (n1 x n2, row-major, rows beyond k included) may be NULL.
+ *   pgx_fcd_match      HOST lists in the layout of pgx_fcd_fetch (n + 1 offsets, the first 0); an offset out of order or an
+ *                      index outside the table fails with PGX_ERR_INVALID before anything runs. Synchronises the
+ *                      context's stream.
+ *   pgx_fcd_match_dev  DEVICE bit masks, concept-major: the row mask of concept i is the pgx_bitmap_stride_words(n_rows)
+ *                      words at i * stride (bit r & 63 of word r >> 6 = row r), column masks likewise with n_cols; 16-byte
+ *                      aligned, pad bits zero, not written. d_match int64[k], d_overlap uint64[k], d_total uint64, a
+ *                      workspace of pgx_fcd_match_workspace_bytes() (16-byte aligned). No allocation, no synchronisation,
+ *                      plain launches on `stream` only: graph-capturable. Nothing the caller passes is used as an index.
+ * Both refuse (PGX_ERR_INVALID) n_rows, n_cols, n1 or n2 >= 2^31 and n_rows * n_cols * k >= 2^63 (total could overflow);
+ * pgx_fcd_match_workspace_bytes returns 0 for those. n1 == 0 or n2 == 0: total = 0 and no kernel runs. The workspace is
+ * (each part rounded up to 256 bytes; stride_r/c = pgx_bitmap_stride_words(n_rows / n_cols)):
+ *   masks of F2  n2 * stride_r * 8 + n2 * stride_c * 8     masks of a block of F1  256 * stride_r * 8 + 256 * stride_c * 8
+ *   a block of O  256 * n2 * 8                             unmatched flags  n2           (the result record is d_total) */
 #define PGX_FCD_OVERLAP 1u
 #define PGX_FCD_DIM_BALANCE 2u
 typedef struct pgx_fcd_info_t {
@@ -531,6 +553,15 @@ int pgx_fcd_coverage(pgx_ctx *ctx, const int32_t *rows, const int32_t *genomes, 
                      uint32_t n_genomes, const int32_t *concept_rows, const uint64_t *row_offsets, const int32_t *concept_cols,
                      const uint64_t *col_offsets, uint64_t n_concepts, uint64_t *out_cleared, uint64_t *out_ones,
                      uint64_t *out_duplicates);
+size_t pgx_fcd_match_workspace_bytes(uint32_t n_rows, uint32_t n_cols, uint64_t n1, uint64_t n2);
+int pgx_fcd_match(pgx_ctx *ctx, uint32_t n_rows, uint32_t n_cols, const int32_t *rows1, const uint64_t *row_off1,
+                  const int32_t *cols1, const uint64_t *col_off1, uint64_t n1, const int32_t *rows2, const uint64_t *row_off2,
+                  const int32_t *cols2, const uint64_t *col_off2, uint64_t n2, int64_t *out_match, uint64_t *out_overlap,
+                  uint64_t *out_total, uint64_t *out_matrix);
+int pgx_fcd_match_dev(pgx_ctx *ctx, const uint64_t *d_row_masks1, const uint64_t *d_col_masks1, uint64_t n1,
+                      const uint64_t *d_row_masks2, const uint64_t *d_col_masks2, uint64_t n2, uint32_t n_rows,
+                      uint32_t n_cols, int64_t *d_match, uint64_t *d_overlap, uint64_t *d_total, uint64_t *d_matrix,
+                      void *d_workspace, size_t workspace_bytes, void *stream);
 
 /* The association screen (reference sparse_utils.py:73-109 compress_rows_spmatrix, ml_pipelines.py:349-388
  * contingency_tables_from_sparse, :233-284 prepare_amr_case_data) on the table restricted to n_selected genomes

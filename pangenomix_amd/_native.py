@@ -155,6 +155,11 @@ SIGNATURES = {
     'pgx_fcd_fetch': (C.c_int, [_P, _P, _P, _P, _P, _P]),
     'pgx_fcd_coverage': (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P, _P, _P, C.c_uint64, _P,
                                    C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    'pgx_fcd_match_workspace_bytes': (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64]),
+    'pgx_fcd_match': (C.c_int, [_P, C.c_uint32, C.c_uint32, _P, _P, _P, _P, C.c_uint64, _P, _P, _P, _P, C.c_uint64, _P, _P,
+                                C.POINTER(C.c_uint64), _P]),
+    'pgx_fcd_match_dev': (C.c_int, [_P, _P, _P, C.c_uint64, _P, _P, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P,
+                                    C.c_size_t, _P]),
     'pgx_assoc_workspace_bytes': (C.c_size_t, [C.c_uint32, C.c_uint32]),
     'pgx_assoc': (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32, _P, _P,
                             _P, _P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
@@ -659,6 +664,48 @@ class Context(object):
                                      _ptr(concept_rows), _ptr(row_offsets), _ptr(concept_cols), _ptr(col_offsets), n,
                                      _ptr(cleared), C.byref(ones), C.byref(dup)))
         return cleared, int(ones.value), int(dup.value)
+
+    @staticmethod
+    def _fcd_match_sizes(n_rows, n_cols, n1, n2):
+        sizes = tuple(int(x) for x in (n_rows, n_cols, n1, n2))
+        if not all(0 <= x < 2 ** 32 for x in sizes):           # (the library refuses 2^31 and above with its own message)
+            raise ValueError('table or concept list too large')
+        return sizes
+
+    def fcd_match(self, n_rows, n_cols, rows1, row_off1, cols1, col_off1, rows2, row_off2, cols2, col_off2, matrix=False):
+        """(match int64[k], overlap uint64[k], total, O or None): the greedy pairing of two concept lists of an
+        n_rows x n_cols table, each as fcd_coverage takes them (pgx.h: pgx_fcd_match); matrix=True also returns the whole
+        n1 x n2 uint64 overlap matrix."""
+        fam = []
+        for idx, off in ((rows1, row_off1), (cols1, col_off1), (rows2, row_off2), (cols2, col_off2)):
+            idx = np.ascontiguousarray(idx, dtype=np.int32)
+            off = np.ascontiguousarray(off, dtype=np.uint64)
+            if idx.ndim != 1 or off.ndim != 1 or off.size < 1 or int(off[-1]) != idx.size:
+                raise ValueError('offsets do not match the concept arrays')
+            fam.append((idx, off))
+        n1, n2 = fam[0][1].size - 1, fam[2][1].size - 1
+        if fam[1][1].size != n1 + 1 or fam[3][1].size != n2 + 1:
+            raise ValueError('row and column offsets of a list differ in length')
+        n_rows, n_cols, n1, n2 = self._fcd_match_sizes(n_rows, n_cols, n1, n2)
+        k = min(n1, n2)
+        match, overlap = np.zeros(k, dtype=np.int64), np.zeros(k, dtype=np.uint64)
+        total = C.c_uint64(0)
+        O = np.zeros((n1, n2), dtype=np.uint64) if matrix else None
+        check(lib().pgx_fcd_match(self._h, n_rows, n_cols, _ptr(fam[0][0]), _ptr(fam[0][1]), _ptr(fam[1][0]), _ptr(fam[1][1]),
+                                  n1, _ptr(fam[2][0]), _ptr(fam[2][1]), _ptr(fam[3][0]), _ptr(fam[3][1]), n2, _ptr(match),
+                                  _ptr(overlap), C.byref(total), _ptr(O)))
+        return match, overlap, int(total.value), O
+
+    def fcd_match_workspace_bytes(self, n_rows, n_cols, n1, n2):
+        return int(lib().pgx_fcd_match_workspace_bytes(*self._fcd_match_sizes(n_rows, n_cols, n1, n2)))
+
+    def fcd_match_dev(self, d_row_masks1, d_col_masks1, n1, d_row_masks2, d_col_masks2, n2, n_rows, n_cols, d_match,
+                      d_overlap, d_total, d_ws, ws_bytes, d_matrix=None, stream=0):
+        """The same on bit masks in device memory (raw device addresses; concept-major, see pgx.h: pgx_fcd_match_dev).
+        Nothing is allocated and nothing synchronised: the results are in the caller's buffers in stream order."""
+        n_rows, n_cols, n1, n2 = self._fcd_match_sizes(n_rows, n_cols, n1, n2)
+        check(lib().pgx_fcd_match_dev(self._h, d_row_masks1, d_col_masks1, n1, d_row_masks2, d_col_masks2, n2, n_rows, n_cols,
+                                      d_match, d_overlap, d_total, d_matrix, d_ws, int(ws_bytes), stream))
 
     # -- association screen (sparse_utils.compress_rows*, ml_pipelines.contingency_tables_from_sparse) -------------------
     @staticmethod

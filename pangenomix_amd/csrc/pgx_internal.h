@@ -47,6 +47,8 @@ enum DevSlot : int {        // pgx_ctx::arena, through DevBuf
     // fcd.hip
     FC_SLOT_BITS, FC_SLOT_ROWS, FC_SLOT_GENOMES, FC_SLOT_CNT, FC_SLOT_WS, FC_SLOT_MAP, FC_SLOT_CMAP, FC_SLOT_CROWS,
     FC_SLOT_CCOLS, FC_SLOT_CLEARED,
+    // fcd_match.hip: the uploaded lists, the workspace, the results, the whole overlap matrix when it is asked for
+    FC_SLOT_M_LISTS, FC_SLOT_M_WS, FC_SLOT_M_OUT, FC_SLOT_M_MATRIX,
     // assoc.hip
     AS_SLOT_BITS, AS_SLOT_ROWS, AS_SLOT_GENOMES, AS_SLOT_CNT, AS_SLOT_WS, AS_SLOT_RMAP, AS_SLOT_CMAP, AS_SLOT_MASKS,
     AS_SLOT_TP, AS_SLOT_INC, AS_SLOT_BLOCK, AS_SLOT_REP,

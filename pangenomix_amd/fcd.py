@@ -12,8 +12,13 @@ popcount over the genome-major bitmap libpgx builds and keeps resident (pangenom
 reference copies a dense int64 block with np.ix_ and sums it. The table goes to the device as coordinates and is never
 densified here; the shuffle of `seed` is numpy's own, on the host. There is no CPU fallback.
 
-The helpers around it (decompose / encode / similarity / sort / load / save) are plain numpy, as in the reference;
+The helpers around it (decompose / encode / sort / load / save) are plain numpy, as in the reference;
 `compute_concept_coverage` clears the concepts' blocks on the device with the kernel the decomposition uses.
+
+`compute_concept_list_similarity` is the reference's host loop unless it is given a context: then the two lists become
+row and column bit masks on the device, the cells every pair of concepts shares are an AND + popcount product, and the
+greedy pairing runs there too (pangenomix_amd/csrc/fcd_match.hip). `match_concept_lists` returns that pairing, which the
+reference throws away, and `concept_overlaps` the whole overlap matrix.
 """
 
 from __future__ import print_function
@@ -185,9 +190,51 @@ def encode_from_concepts(F):
     return H
 
 
-def compute_concept_list_similarity(F1, F2, S):
+def _match(F1, F2, shape, ctx, matrix):
+    n_rows, n_cols = (int(x) for x in shape)
+    lists = _flatten(F1) + _flatten(F2)
+    for name, bound, parts in (('row', n_rows, lists[0::4]), ('column', n_cols, lists[2::4])):
+        for idx in parts:
+            if idx.size and (idx.min() < 0 or idx.max() >= bound):
+                raise IndexError('a concept names a %s outside the table' % name)
+    ctx = ctx or _native.default_context()
+    return ctx.fcd_match(n_rows, n_cols, *lists, matrix=matrix)
+
+
+def match_concept_lists(F1, F2, shape, ctx=None):
+    """The pairing compute_concept_list_similarity makes and throws away, on the device: (match, overlap, total) with
+    match[i] = the concept of F2 paired with F1[i] and overlap[i] = the cells the two share (int64 arrays of
+    min(len(F1), len(F2)) entries), total = sum(overlap) as a Python int. Every concept of F1, in order, takes the
+    unmatched concept of F2 it shares the most cells with, the lowest index among equals; sharing nothing still takes
+    one. shape = (rows, columns) of the table; an index outside it raises IndexError. A concept is a set: an index
+    listed twice counts once."""
+    match, overlap, total, _ = _match(F1, F2, shape, ctx, False)
+    return match, overlap.astype(np.int64), total
+
+
+def concept_overlaps(F1, F2, shape, ctx=None):
+    """O[i][j] = the cells F1[i] and F2[j] share (rows in common x columns in common): len(F1) x len(F2), int64."""
+    return _match(F1, F2, shape, ctx, True)[3].astype(np.int64)
+
+
+def _ones(S):
+    """the denominator of the similarity score, the reference's expression"""
+    if isinstance(S, sparse_utils.LightSparseDataFrame):
+        return float(np.sum(S.data.data))
+    return float(np.sum(S))
+
+
+def compute_concept_list_similarity(F1, F2, S, ctx=None):
     """How alike two decompositions are: every concept of F1, in order, is paired with the unmatched concept of F2 it
-    shares the most cells with (the first among equals); the score is the cells shared by the pairs over the ones of S."""
+    shares the most cells with (the first among equals); the score is the cells shared by the pairs over the ones of S.
+
+    Without `ctx` this is the reference's double loop over pairs of Python sets, on the host. With a
+    pangenomix_amd._native.Context the pairing runs on the device (match_concept_lists, which also returns the pairs);
+    the division stays Python's, so the score has the same bits and an all-zero S raises ZeroDivisionError either way.
+    On that path S may also be a LightSparseDataFrame, and an index outside S raises IndexError."""
+    if ctx is not None:
+        return _match(F1, F2, S.shape, ctx, False)[2] / _ones(S)
+
     def shared(C1, C2):
         return len(set(C1[0]).intersection(C2[0])) * len(set(C1[1]).intersection(C2[1]))
 
