@@ -26,6 +26,8 @@
  *                                       per-phenotype association screen -> pgx_assoc*
  *   pangenome.py:1246-1330, :1812-1889  validate_gene_table[_dense]() / extract_dominant_alleles(): the Python loops
  *                                       over allele rows or genome columns -> pgx_allele_runs*
+ *   core_genome.py:7-26, allele_identification.py:7-20   create_core_genes_fasta() / create_alleles_fasta(): the
+ *                                       iterrows() loops that pick one allele per gene -> pgx_core_select*
  *
  * The reference-side binding is a ctypes stub. Conventions:
  *   - every function returns 0 on success and a negative pgx_status on error;
@@ -636,6 +638,43 @@ int pgx_allele_runs_dev(pgx_ctx *ctx, const uint64_t *d_allele_bits, uint32_t n_
                         const int32_t *d_gene_of_run, uint64_t *d_derived, uint64_t *d_diff, uint32_t *d_diff_per_genome,
                         uint32_t *d_diff_per_run, uint64_t *d_total, int32_t *d_best_allele, uint32_t *d_best_count,
                         void *d_workspace, size_t workspace_bytes, void *stream);
+
+/* Core / dominant allele selection (reference core_genome.py:7-26 create_core_genes_fasta, allele_identification.py:7-20
+ * create_alleles_fasta): the runs, tables and rules of "Runs of allele rows" above, and thresholds[n_thresholds] (uint32,
+ * 1 <= n_thresholds <= 32, in any order, repeats allowed).
+ *   gene_count   [n_runs] uint32: set bits of row gene_of_run[r] of the gene table; 0 for -1, and 0 everywhere without
+ *                gene_of_run or (device entry) without a gene bitmap
+ *   best_allele  [n_runs] int32 / best_count [n_runs] uint32: as pgx_allele_runs gives them (the same code)
+ *   mask         [n_runs] uint32: bit t is set iff the run is eligible and gene_count[r] >= thresholds[t]; a run is eligible
+ *                iff best_allele[r] >= 0 and gene_of_run[r] >= 0 -- with gene_of_run NULL, iff best_allele[r] >= 0
+ *   selected     [n_thresholds x n_runs] int32, n_selected [n_thresholds] uint32: row t of selected holds best_allele[r] of
+ *                the runs with bit t, in ascending r; entries at and beyond n_selected[t] are NOT written
+ * Every output pointer may be NULL; what is not asked for is not computed. No atomics on a result: the same inputs give
+ * the same bytes whatever order the device's waves run in.
+ *   pgx_core_select      HOST COO coordinates of both tables (the gene table is used only with gene_of_run), host run
+ *                        arrays, thresholds and results; out_duplicates as pgx_allele_runs (2 x uint64, may be NULL): with
+ *                        duplicate coordinates in either table nothing is computed. Run arrays that break the rules,
+ *                        n_thresholds outside 1..32, or n_runs = 0 with an output requested fail with PGX_ERR_INVALID
+ *                        before anything is launched.
+ *   pgx_core_select_dev  the bitmaps, run arrays, thresholds, results and the workspace
+ *                        (pgx_core_select_workspace_bytes(), 16-byte aligned) are the caller's DEVICE pointers. Plain
+ *                        launches on `stream`, which is synchronised once at the end. The run arrays are checked on the
+ *                        device: the kernels clamp what they read (a gene row out of range counts as none), and arrays that
+ *                        break the rules fail with PGX_ERR_INVALID after the launches, the outputs then being unspecified.
+ * pgx_core_select_block(): the runs one workgroup takes. n_alleles, n_runs, n_genes, n_genomes < 2^31. */
+uint32_t pgx_core_select_block(void);
+size_t pgx_core_select_workspace_bytes(uint32_t n_alleles, uint32_t n_genes, uint32_t n_runs);
+int pgx_core_select(pgx_ctx *ctx, const int32_t *allele_rows, const int32_t *allele_genomes, uint64_t n_allele_records,
+                    uint32_t n_alleles, const int32_t *gene_rows, const int32_t *gene_genomes, uint64_t n_gene_records,
+                    uint32_t n_genes, uint32_t n_genomes, const uint32_t *run_start, uint32_t n_runs, const int32_t *gene_of_run,
+                    const uint32_t *thresholds, uint32_t n_thresholds, uint32_t *out_gene_count, int32_t *out_best_allele,
+                    uint32_t *out_best_count, uint32_t *out_mask, int32_t *out_selected, uint32_t *out_n_selected,
+                    uint64_t *out_duplicates);
+int pgx_core_select_dev(pgx_ctx *ctx, const uint64_t *d_allele_bits, uint32_t n_alleles, const uint64_t *d_gene_bits,
+                        uint32_t n_genes, uint32_t n_genomes, const uint32_t *d_run_start, uint32_t n_runs,
+                        const int32_t *d_gene_of_run, const uint32_t *d_thresholds, uint32_t n_thresholds,
+                        uint32_t *d_gene_count, int32_t *d_best_allele, uint32_t *d_best_count, uint32_t *d_mask,
+                        int32_t *d_selected, uint32_t *d_n_selected, void *d_workspace, size_t workspace_bytes, void *stream);
 
 /* Exact search for fixed-length keys in a text (reference pangenome.py:1573-1647 validate_proximal_table_direct, which slides a
  * window over every contig): text is text_bytes raw bytes, keys n_keys x window raw bytes, found [n_keys] uint8:

@@ -172,6 +172,12 @@ SIGNATURES = {
                                   _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'pgx_allele_runs_dev': (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, _P, _P, _P, _P, _P,
                                       _P, _P, _P, C.c_size_t, _P]),
+    'pgx_core_select_block': (C.c_uint32, []),
+    'pgx_core_select_workspace_bytes': (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_uint32]),
+    'pgx_core_select': (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint32, _P, _P, C.c_uint64, C.c_uint32, C.c_uint32, _P, C.c_uint32,
+                                  _P, _P, C.c_uint32, _P, _P, _P, _P, _P, _P, _P]),
+    'pgx_core_select_dev': (C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P,
+                                      _P, _P, _P, _P, _P, C.c_size_t, _P]),
     'pgx_window_scan_tile': (C.c_uint32, []),
     'pgx_window_scan_workspace_bytes': (C.c_size_t, [C.c_uint64, C.c_uint32, C.c_uint32]),
     'pgx_window_scan': (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P]),
@@ -822,6 +828,58 @@ class Context(object):
         check(lib().pgx_allele_runs_dev(self._h, d_allele_bits, int(n_alleles), d_gene_bits, int(n_genes), int(n_genomes),
                                         d_run_start, int(n_runs), d_gene_of_run, d_derived, d_diff, d_diff_per_genome,
                                         d_diff_per_run, d_total, d_best_allele, d_best_count, d_ws, int(ws_bytes), stream))
+
+    # -- core / dominant allele selection (core_genome.create_core_genes_fasta, allele_identification.create_alleles_fasta) --
+    SELECT_OUTPUTS = ('gene_count', 'best_allele', 'best_count', 'mask', 'selected', 'n_selected')
+
+    def core_select(self, allele_rows, allele_genomes, n_alleles, n_genomes, run_start, thresholds, gene_rows=None,
+                    gene_genomes=None, n_genes=0, gene_of_run=None, want=SELECT_OUTPUTS):
+        """({name: array for name in want}, (allele duplicates, gene duplicates)) of the runs [run_start[r], run_start[r + 1])
+        of the allele table's rows and up to 32 uint32 thresholds (pgx.h: pgx_core_select). 'gene_count' / 'best_count' /
+        'mask' are uint32 [n_runs], 'best_allele' int32 [n_runs], 'n_selected' uint32 [n_thresholds]; 'selected' is a list
+        of n_thresholds int32 arrays, row t cut to n_selected[t]. With duplicate coordinates nothing is computed and the
+        dict is None."""
+        a_rows, a_genomes = _coo_args(allele_rows, allele_genomes)
+        run_start = np.ascontiguousarray(run_start, dtype=np.uint32)
+        if run_start.ndim != 1 or run_start.size < 1:
+            raise ValueError('run_start must hold n_runs + 1 entries')
+        thresholds = np.ascontiguousarray(thresholds, dtype=np.uint32)
+        if thresholds.ndim != 1:
+            raise ValueError('thresholds must be one-dimensional')
+        n_runs, n_thr = run_start.size - 1, thresholds.size
+        g_rows = g_genomes = None
+        if gene_of_run is not None:
+            gene_of_run = np.ascontiguousarray(gene_of_run, dtype=np.int32)
+            if gene_of_run.shape != (n_runs,):
+                raise ValueError('gene_of_run must hold one entry per run')
+            g_rows, g_genomes = _coo_args(gene_rows if gene_rows is not None else [], gene_genomes if gene_genomes is not None else [])
+        unknown = set(want) - set(self.SELECT_OUTPUTS)
+        if unknown:
+            raise ValueError('unknown outputs %r' % sorted(unknown))
+        want = set(want) | ({'n_selected'} if 'selected' in want else set())
+        shapes = {'gene_count': (n_runs, np.uint32), 'best_allele': (n_runs, np.int32), 'best_count': (n_runs, np.uint32),
+                  'mask': (n_runs, np.uint32), 'selected': ((n_thr, n_runs), np.int32), 'n_selected': (n_thr, np.uint32)}
+        out = {k: (np.empty if k == 'selected' else np.zeros)(*shapes[k]) for k in self.SELECT_OUTPUTS if k in want}
+        dup = np.zeros(2, dtype=np.uint64)
+        check(lib().pgx_core_select(self._h, _ptr(a_rows), _ptr(a_genomes), a_rows.size, int(n_alleles), _ptr(g_rows),
+                                    _ptr(g_genomes), 0 if g_rows is None else g_rows.size, int(n_genes), int(n_genomes),
+                                    _ptr(run_start), n_runs, _ptr(gene_of_run), _ptr(thresholds), n_thr,
+                                    *([_ptr(out.get(k)) for k in self.SELECT_OUTPUTS] + [_ptr(dup)])))
+        dups = (int(dup[0]), int(dup[1]))
+        if any(dups):
+            return None, dups
+        if 'selected' in out:
+            out['selected'] = [out['selected'][t, :int(out['n_selected'][t])].copy() for t in range(n_thr)]
+        return out, dups
+
+    def core_select_dev(self, d_allele_bits, n_alleles, d_gene_bits, n_genes, n_genomes, d_run_start, n_runs, d_gene_of_run,
+                        d_thresholds, n_thresholds, d_gene_count, d_best_allele, d_best_count, d_mask, d_selected,
+                        d_n_selected, d_ws, ws_bytes, stream=0):
+        """The same on device memory (raw device addresses, None for what is not wanted; synchronises `stream`, see pgx.h)."""
+        check(lib().pgx_core_select_dev(self._h, d_allele_bits, int(n_alleles), d_gene_bits, int(n_genes), int(n_genomes),
+                                        d_run_start, int(n_runs), d_gene_of_run, d_thresholds, int(n_thresholds), d_gene_count,
+                                        d_best_allele, d_best_count, d_mask, d_selected, d_n_selected, d_ws, int(ws_bytes),
+                                        stream))
 
     # -- fixed-length keys in a text (pangenome.validate_proximal_table_direct) ---------------------------------------------
     def window_scan(self, text, keys, flags=0):

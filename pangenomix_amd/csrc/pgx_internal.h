@@ -56,6 +56,9 @@ enum DevSlot : int {        // pgx_ctx::arena, through DevBuf
     RN_SLOT_ABITS, RN_SLOT_AROWS, RN_SLOT_AGENOMES, RN_SLOT_ACNT, RN_SLOT_GBITS, RN_SLOT_GROWS, RN_SLOT_GGENOMES,
     RN_SLOT_GCNT, RN_SLOT_WS, RN_SLOT_START, RN_SLOT_GENE, RN_SLOT_DERIVED, RN_SLOT_DIFF, RN_SLOT_PER_GENOME,
     RN_SLOT_PER_RUN, RN_SLOT_TOTAL, RN_SLOT_BEST, RN_SLOT_BEST_COUNT,
+    // select.hip: the two tables as runs.hip keeps them, the workspace, the run arrays, the thresholds, every result in one
+    CS_SLOT_ABITS, CS_SLOT_AROWS, CS_SLOT_AGENOMES, CS_SLOT_ACNT, CS_SLOT_GBITS, CS_SLOT_GROWS, CS_SLOT_GGENOMES,
+    CS_SLOT_GCNT, CS_SLOT_WS, CS_SLOT_START, CS_SLOT_GENE, CS_SLOT_THR, CS_SLOT_OUT,
     // scan.hip
     SC_SLOT_TEXT, SC_SLOT_KEYS, SC_SLOT_FOUND, SC_SLOT_WS,
     // bernoulli_cd.hip
@@ -74,6 +77,7 @@ enum HostSlot : int {       // pgx_ctx::host_scratch, through HostVec
     FC_HOST_RES,
     AS_HOST_STATUS,
     RN_HOST_STATUS,
+    CS_HOST_STATUS,
     HOST_SLOT_COUNT
 };
 enum PinSlot : int {        // pgx_ctx::host_arena, through Pinned (cluster.hip)
@@ -307,3 +311,17 @@ int pgx_gather_resident(pgx_ctx *ctx, const ResidentBitmap &src, const int32_t *
 
 // all-gather of `count` uint64 per process with the context's RCCL communicator, enqueued on `stream` (rccl_exchange.hip)
 int pgx_rccl_all_gather_u64(pgx_ctx *ctx, const void *send, void *recv, size_t count, hipStream_t stream);
+
+// What select.hip takes from runs.hip. The rules of the run arrays (pgx.h, "Runs of allele rows"): the message of the first
+// one broken or NULL -- of host arrays, and of the status word pgx_runs_check_enqueue ORs its findings into (the caller
+// zeroes it first and reads it back after its launches). pgx_runs_stats_enqueue: the allele rows' counts into d_counts
+// (n_alleles x int32), then total / best_allele / best_count of every run (each may be NULL), reads clamped to n_alleles.
+// Both only enqueue on `stream`.
+const char *pgx_runs_host_error(const uint32_t *run_start, uint32_t n_runs, const int32_t *gene_of_run, uint32_t n_alleles,
+                                uint32_t n_genes);
+const char *pgx_runs_status_error(uint32_t status);
+int pgx_runs_check_enqueue(pgx_ctx *ctx, const uint32_t *d_run_start, const int32_t *d_gene_of_run, uint32_t n_runs,
+                           uint32_t n_alleles, uint32_t n_genes, uint32_t *d_status, hipStream_t stream);
+int pgx_runs_stats_enqueue(pgx_ctx *ctx, const uint64_t *d_abits, uint32_t n_alleles, uint32_t n_genomes,
+                           const uint32_t *d_run_start, uint32_t n_runs, int32_t *d_counts, uint64_t *d_total,
+                           int32_t *d_best_allele, uint32_t *d_best_count, hipStream_t stream);

@@ -150,6 +150,53 @@ __global__ __launch_bounds__(RN_THREADS) void runs_stats_kernel(const int32_t *_
     if (best_count) best_count[r] = top;
 }
 
+}  // namespace
+
+// ---- what select.hip shares with this file (pgx_internal.h) ----
+const char *pgx_runs_host_error(const uint32_t *run_start, uint32_t n_runs, const int32_t *gene_of_run, uint32_t n_alleles,
+                                uint32_t n_genes) {
+    if (n_runs && run_start[0] != 0) return "run_start must start at 0 and never decrease";
+    for (uint32_t r = 0; r < n_runs; ++r) {
+        if (run_start[r] > run_start[r + 1]) return "run_start must start at 0 and never decrease";
+        if (gene_of_run && !(gene_of_run[r] >= -1 && (gene_of_run[r] < 0 || (uint32_t)gene_of_run[r] < n_genes)))
+            return "gene_of_run entry out of range";
+    }
+    if (n_runs && run_start[n_runs] > n_alleles) return "run_start ends beyond the allele rows";
+    return nullptr;
+}
+
+const char *pgx_runs_status_error(uint32_t status) {
+    if (status & RN_ERR_ORDER) return "run_start must start at 0 and never decrease";
+    if (status & RN_ERR_END) return "run_start ends beyond the allele rows";
+    if (status & RN_ERR_GENE) return "gene_of_run entry out of range";
+    return nullptr;
+}
+
+int pgx_runs_check_enqueue(pgx_ctx *ctx, const uint32_t *d_run_start, const int32_t *d_gene_of_run, uint32_t n_runs,
+                           uint32_t n_alleles, uint32_t n_genes, uint32_t *d_status, hipStream_t stream) {
+    {
+        ProfScope prof(ctx, "runs_check_kernel", stream);
+        runs_check_kernel<<<ceil_div_u32(n_runs, RN_THREADS), RN_THREADS, 0, stream>>>(d_run_start, d_gene_of_run, n_runs,
+                                                                                      n_alleles, n_genes, d_status);
+    }
+    PGX_HIP(hipGetLastError());
+    return PGX_OK;
+}
+
+int pgx_runs_stats_enqueue(pgx_ctx *ctx, const uint64_t *d_abits, uint32_t n_alleles, uint32_t n_genomes,
+                           const uint32_t *d_run_start, uint32_t n_runs, int32_t *d_counts, uint64_t *d_total,
+                           int32_t *d_best_allele, uint32_t *d_best_count, hipStream_t stream) {
+    const int rc = pgx_row_counts_dev(ctx, d_abits, n_alleles, n_genomes, d_counts, stream);
+    if (rc != PGX_OK) return rc;
+    ProfScope prof(ctx, "runs_stats_kernel", stream);
+    runs_stats_kernel<<<ceil_div_u32(n_runs, RN_THREADS), RN_THREADS, 0, stream>>>(
+        d_counts, n_alleles, d_run_start, n_runs, (unsigned long long *)d_total, d_best_allele, d_best_count);
+    PGX_HIP(hipGetLastError());
+    return PGX_OK;
+}
+
+namespace {
+
 struct RunsOut {
     uint64_t *derived, *diff;
     uint32_t *diff_per_genome, *diff_per_run;
@@ -191,11 +238,8 @@ int runs_run(pgx_ctx *ctx, const uint64_t *d_abits, uint32_t n_alleles, const ui
     const uint32_t run_blocks = ceil_div_u32(n_runs, RN_THREADS);
 
     PGX_HIP(hipMemsetAsync(status, 0, 16, stream));
-    {
-        ProfScope prof(ctx, "runs_check_kernel", stream);
-        runs_check_kernel<<<run_blocks, RN_THREADS, 0, stream>>>(d_run_start, d_gene_of_run, n_runs, n_alleles, n_genes, status);
-    }
-    PGX_HIP(hipGetLastError());
+    rc = pgx_runs_check_enqueue(ctx, d_run_start, d_gene_of_run, n_runs, n_alleles, n_genes, status, stream);
+    if (rc != PGX_OK) return rc;
     if (n_genomes && (out.derived || diff)) {
         if (out.derived) PGX_HIP(hipMemsetAsync(out.derived, 0, out_bytes, stream));
         if (diff) PGX_HIP(hipMemsetAsync(diff, 0, out_bytes, stream));
@@ -216,18 +260,14 @@ int runs_run(pgx_ctx *ctx, const uint64_t *d_abits, uint32_t n_alleles, const ui
         PGX_HIP(hipGetLastError());
     }
     if (out.total || out.best_allele || out.best_count) {
-        rc = pgx_row_counts_dev(ctx, d_abits, n_alleles, n_genomes, counts, stream);
+        rc = pgx_runs_stats_enqueue(ctx, d_abits, n_alleles, n_genomes, d_run_start, n_runs, counts, out.total, out.best_allele,
+                                    out.best_count, stream);
         if (rc != PGX_OK) return rc;
-        ProfScope prof(ctx, "runs_stats_kernel", stream);
-        runs_stats_kernel<<<run_blocks, RN_THREADS, 0, stream>>>(counts, n_alleles, d_run_start, n_runs,
-                                                                 (unsigned long long *)out.total, out.best_allele, out.best_count);
-        PGX_HIP(hipGetLastError());
     }
     PGX_HIP(hipMemcpyAsync(h_status.data(), status, 4, hipMemcpyDeviceToHost, stream));
     PGX_HIP(hipStreamSynchronize(stream));
-    PGX_REQUIRE(!(h_status[0] & RN_ERR_ORDER), "run_start must start at 0 and never decrease");
-    PGX_REQUIRE(!(h_status[0] & RN_ERR_END), "run_start ends beyond the allele rows");
-    PGX_REQUIRE(!(h_status[0] & RN_ERR_GENE), "gene_of_run entry out of range");
+    const char *broken = pgx_runs_status_error(h_status[0]);
+    PGX_REQUIRE(!broken, broken);
     return PGX_OK;
 }
 
@@ -240,13 +280,8 @@ int runs_host(pgx_ctx *ctx, const int32_t *a_rows, const int32_t *a_genomes, uin
     PGX_REQUIRE(a_records == 0 || (a_rows && a_genomes), "NULL record arrays");
     PGX_REQUIRE(!gene_of_run || g_records == 0 || (g_rows && g_genomes), "NULL record arrays");
     // the run arrays are host memory here: refused before anything is uploaded or launched
-    if (n_runs) PGX_REQUIRE(run_start[0] == 0, "run_start must start at 0 and never decrease");
-    for (uint32_t r = 0; r < n_runs; ++r) {
-        PGX_REQUIRE(run_start[r] <= run_start[r + 1], "run_start must start at 0 and never decrease");
-        PGX_REQUIRE(!gene_of_run || (gene_of_run[r] >= -1 && (gene_of_run[r] < 0 || (uint32_t)gene_of_run[r] < n_genes)),
-                    "gene_of_run entry out of range");
-    }
-    PGX_REQUIRE(n_runs == 0 || run_start[n_runs] <= n_alleles, "run_start ends beyond the allele rows");
+    const char *broken = pgx_runs_host_error(run_start, n_runs, gene_of_run, n_alleles, n_genes);
+    PGX_REQUIRE(!broken, broken);
     if (out_duplicates) out_duplicates[0] = out_duplicates[1] = 0;
     PGX_HIP(hipSetDevice(ctx->device_id));
     hipStream_t stream = ctx->stream;
