@@ -603,6 +603,54 @@ int pgx_assoc_dev(pgx_ctx *ctx, const uint64_t *d_bits, uint32_t n_rows, uint32_
                   uint32_t *d_incidence, int32_t *d_block_of_row, int32_t *d_rep_row, void *d_workspace,
                   size_t workspace_bytes, void *stream, uint32_t *out_n_blocks);
 
+/* A bagged ensemble of linear SVMs on the table's genomes (reference ml_pipelines.py:21-98 evaluate_model with sklearn's
+ * BaggingClassifier(LinearSVC)): the samples are the n_genomes genomes, the features the n_rows rows of the bitmap above.
+ *   masks              n_masks feature masks, each pgx_bitmap_stride_words(n_rows) words in the layout of one genome's bits
+ *                      (bit r & 63 of word r >> 6 = row r takes part); bits at or behind n_rows are ignored
+ *   sub-problem p      mask_of_problem[p] (0 .. n_masks - 1), C[p], multiplicity[p * n_genomes + i] = how often genome i
+ *                      was drawn into p's training set (bootstrap draws folded; 0 = not in it); sub-problems that name the
+ *                      same mask share its Gram matrix
+ *   labels[i]          0 or 1, read as y_i = -1 / +1; one vector for all sub-problems
+ * Sub-problem p is LinearSVC(penalty = l2, loss = squared_hinge, dual, fit_intercept, intercept_scaling = 1) on the drawn
+ * genomes, solved in its dual with the copies of a genome summed into one variable b_i >= 0 (genomes with m_i > 0):
+ *   min 1/2 b'Qb - sum b_i,   Q_ij = y_i y_j (K_ij + 1) + [i == j] / (2 C m_i),   K_ij = popcount(bits_i & bits_j & mask)
+ * Q is positive definite (smallest eigenvalue >= 1 / (2 C max m)), the optimum unique. The solver is pinned: greedy dual
+ * coordinate descent in double precision. g = Qb - 1 is kept; PG_i = g_i where b_i > 0, else min(g_i, 0); the i of largest
+ * |PG_i| (ties: the smallest i) takes the step d = max(-b_i, -g_i / Q_ii), b_i += d, g += d Q[:, i]; when max |PG_i| <= tol,
+ * g is recomputed from b in one product in ascending order of i and the test repeated, the descent going on if it fails.
+ * More than max_steps steps (0 = 1,000,000 + 2,000 n_genomes) fail the call with PGX_ERR_INTERNAL, the outputs then
+ * being unspecified. Gram entries are exact integers, every sum runs in a fixed order, there is no floating-point atomic:
+ * the same inputs give the same bits on every call. At the end |PG_i| <= tol for the recomputed g, hence
+ * every b_i, coef and the intercept lie within 2 C max(m) n tol of the optimum's.
+ *   beta       [n_problems x n_genomes]  b_i, 0 where m_i = 0
+ *   coef       [n_problems x n_rows]     sum_i b_i y_i bit(i, r) for the rows r of the mask, 0 outside it
+ *   intercept  [n_problems]              sum_i b_i y_i
+ *   decision   [n_problems x n_genomes]  sum_i b_i y_i (K_si + 1) for EVERY genome s of the table, drawn or not
+ *   steps      [n_problems]              coordinate steps taken
+ * Refused with PGX_ERR_INVALID: n_rows, n_genomes, n_masks or n_problems = 0, tol not finite and positive, a mask index
+ * out of range, a mask without a bit below n_rows, a C that is not finite and positive, a label other than 0 or 1, a
+ * sub-problem whose drawn genomes carry one class only. n_genomes above PGX_SVM_MAX_GENOMES: PGX_ERR_CAPACITY (there is
+ * no slower path). n_rows < 2^30, n_masks and n_problems <= 65535.
+ *   pgx_svm_bag        HOST COO coordinates of the table and host arrays; everything above is checked before anything
+ *                      is launched; then a coordinate out of range or given twice is PGX_ERR_INVALID as well.
+ *   pgx_svm_bag_dev    d_bits: the table in the bitmap layout above (never written); masks, sub-problems, labels and the
+ *                      five results are DEVICE pointers, the workspace the caller's (pgx_svm_bag_workspace_bytes(),
+ *                      16-byte aligned: the Gram matrices, n_masks x n_genomes^2 x 4 bytes, and a status word). The
+ *                      scalars are checked before anything is launched; the arrays are checked on the device (a broken
+ *                      sub-problem is skipped, the outputs are then unspecified). Plain launches on `stream`, which is
+ *                      synchronised once at the end (the status back). Nothing is allocated. */
+#define PGX_SVM_MAX_GENOMES 4096u
+size_t pgx_svm_bag_workspace_bytes(uint32_t n_rows, uint32_t n_genomes, uint32_t n_masks);
+int pgx_svm_bag(pgx_ctx *ctx, const int32_t *rows, const int32_t *genomes, uint64_t n_records, uint32_t n_rows,
+                uint32_t n_genomes, const uint64_t *masks, uint32_t n_masks, const int32_t *mask_of_problem, const double *C,
+                const uint16_t *multiplicity, uint32_t n_problems, const uint8_t *labels, double tol, uint32_t max_steps,
+                double *out_beta, double *out_coef, double *out_intercept, double *out_decision, uint32_t *out_steps);
+int pgx_svm_bag_dev(pgx_ctx *ctx, const uint64_t *d_bits, uint32_t n_rows, uint32_t n_genomes, const uint64_t *d_masks,
+                    uint32_t n_masks, const int32_t *d_mask_of_problem, const double *d_C, const uint16_t *d_multiplicity,
+                    uint32_t n_problems, const uint8_t *d_labels, double tol, uint32_t max_steps, double *d_beta,
+                    double *d_coef, double *d_intercept, double *d_decision, uint32_t *d_steps, void *d_workspace,
+                    size_t workspace_bytes, void *stream);
+
 /* Runs of allele rows (reference pangenome.py:1246-1330 validate_gene_table / validate_gene_table_dense, :1812-1889
  * extract_dominant_alleles): run r is the allele rows [run_start[r], run_start[r + 1]) of the allele table -- run_start holds
  * n_runs + 1 entries, starts at 0, never decreases and ends at or below n_alleles; a run may be empty, rows behind the last

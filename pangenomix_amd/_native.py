@@ -167,6 +167,11 @@ SIGNATURES = {
                                      _P, _P, _P, _P, C.POINTER(C.c_uint32)]),
     'pgx_assoc_dev': (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P,
                                 C.c_size_t, _P, C.POINTER(C.c_uint32)]),
+    'pgx_svm_bag_workspace_bytes': (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_uint32]),
+    'pgx_svm_bag': (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, _P, _P, C.c_uint32, _P,
+                              C.c_double, C.c_uint32, _P, _P, _P, _P, _P]),
+    'pgx_svm_bag_dev': (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P, _P, _P, C.c_uint32, _P, C.c_double,
+                                  C.c_uint32, _P, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     'pgx_allele_runs_workspace_bytes': (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_uint32]),
     'pgx_allele_runs': (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint32, _P, _P, C.c_uint64, C.c_uint32, C.c_uint32, _P, C.c_uint32,
                                   _P, _P, _P, _P, _P, _P, _P, _P, _P]),
@@ -783,6 +788,48 @@ class Context(object):
                                   int(n_targets), flags, d_tp, d_incidence, d_block_of_row, d_rep_row, d_ws, int(ws_bytes),
                                   stream, C.byref(n_blocks)))
         return int(n_blocks.value)
+
+    # -- bagged linear SVMs in the dual (ml_pipelines.BaggedLinearSVC / evaluate_model) ------------------------------------
+    SVM_MAX_GENOMES = 4096                   # PGX_SVM_MAX_GENOMES
+
+    def svm_bag(self, rows, genomes, n_rows, n_genomes, masks, mask_of_problem, C_values, multiplicity, labels, tol=1e-10,
+                max_steps=0):
+        """{'beta' [P, n_genomes], 'coef' [P, n_rows], 'intercept' [P], 'decision' [P, n_genomes] float64, 'steps' uint32 [P]}
+        of the P sub-problems {mask_of_problem[p], C_values[p], multiplicity[p]} on the binary table with the given COO
+        coordinates (rows = features, genomes = samples), labels uint8 [n_genomes] (pgx.h: pgx_svm_bag). masks: uint64
+        [n_masks, stride_words(n_rows)]. max_steps = 0: the library's default."""
+        rows, genomes = _coo_args(rows, genomes)
+        n_rows, n_genomes = int(n_rows), int(n_genomes)
+        stride = int(lib().pgx_bitmap_stride_words(n_rows))
+        masks = np.ascontiguousarray(masks, dtype=np.uint64)
+        if masks.ndim != 2 or masks.shape[1] != stride:
+            raise ValueError('masks must be [n_masks, %d] words' % stride)
+        mask_of_problem = np.ascontiguousarray(mask_of_problem, dtype=np.int32)
+        C_values = np.ascontiguousarray(C_values, dtype=np.float64)
+        multiplicity = np.ascontiguousarray(multiplicity, dtype=np.uint16)
+        labels = np.ascontiguousarray(labels, dtype=np.uint8)
+        P = int(mask_of_problem.size)
+        if mask_of_problem.ndim != 1 or C_values.shape != (P,) or multiplicity.shape != (P, n_genomes) or \
+                labels.shape != (n_genomes,):
+            raise ValueError('one mask index, one C and n_genomes multiplicities per sub-problem; one label per genome')
+        out = {'beta': np.zeros((P, n_genomes)), 'coef': np.zeros((P, n_rows)), 'intercept': np.zeros(P),
+               'decision': np.zeros((P, n_genomes)), 'steps': np.zeros(P, dtype=np.uint32)}
+        check(lib().pgx_svm_bag(self._h, _ptr(rows), _ptr(genomes), rows.size, n_rows, n_genomes, _ptr(masks),
+                                int(masks.shape[0]), _ptr(mask_of_problem), _ptr(C_values), _ptr(multiplicity), P, _ptr(labels),
+                                float(tol), int(max_steps), _ptr(out['beta']), _ptr(out['coef']), _ptr(out['intercept']),
+                                _ptr(out['decision']), _ptr(out['steps'])))
+        return out
+
+    def svm_bag_workspace_bytes(self, n_rows, n_genomes, n_masks):
+        return int(lib().pgx_svm_bag_workspace_bytes(int(n_rows), int(n_genomes), int(n_masks)))
+
+    def svm_bag_dev(self, d_bits, n_rows, n_genomes, d_masks, n_masks, d_mask_of_problem, d_C, d_multiplicity, n_problems,
+                    d_labels, d_beta, d_coef, d_intercept, d_decision, d_steps, d_ws, ws_bytes, tol=1e-10, max_steps=0,
+                    stream=0):
+        """The same on device memory (raw device addresses; synchronises `stream` once at the end, see pgx.h)."""
+        check(lib().pgx_svm_bag_dev(self._h, d_bits, int(n_rows), int(n_genomes), d_masks, int(n_masks), d_mask_of_problem,
+                                    d_C, d_multiplicity, int(n_problems), d_labels, float(tol), int(max_steps), d_beta,
+                                    d_coef, d_intercept, d_decision, d_steps, d_ws, int(ws_bytes), stream))
 
     # -- runs of allele rows (pangenome.validate_gene_table[_dense], extract_dominant_alleles) -----------------------------
     RUNS_OUTPUTS = ('derived', 'diff', 'diff_per_genome', 'diff_per_run', 'total', 'best_allele', 'best_count')

@@ -66,6 +66,8 @@ enum DevSlot : int {        // pgx_ctx::arena, through DevBuf
     // dict.hip: the loaded set stays in the first three; then pgx_genome_sets_diff
     DM_SLOT_KEYS, DM_SLOT_KEY_OFF, DM_SLOT_TABLE, DM_SLOT_QUERIES, DM_SLOT_QUERY_OFF, DM_SLOT_OUT,
     SD_SLOT_ROWS, SD_SLOT_GENOMES, SD_SLOT_A_BITS, SD_SLOT_A_CNT, SD_SLOT_B_BITS, SD_SLOT_B_CNT, SD_SLOT_OUT,
+    // svm.hip: the table, the workspace (Gram matrices, status), every uploaded input in one, every result in one
+    SV_SLOT_BITS, SV_SLOT_ROWS, SV_SLOT_GENOMES, SV_SLOT_CNT, SV_SLOT_WS, SV_SLOT_IN, SV_SLOT_OUT,
     DEV_SLOT_COUNT
 };
 enum HostSlot : int {       // pgx_ctx::host_scratch, through HostVec
@@ -78,6 +80,7 @@ enum HostSlot : int {       // pgx_ctx::host_scratch, through HostVec
     AS_HOST_STATUS,
     RN_HOST_STATUS,
     CS_HOST_STATUS,
+    SV_HOST_STATUS,
     HOST_SLOT_COUNT
 };
 enum PinSlot : int {        // pgx_ctx::host_arena, through Pinned (cluster.hip)
