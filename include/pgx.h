@@ -798,6 +798,57 @@ int pgx_genome_sets_diff(pgx_ctx *ctx, const int32_t *a_rows, const int32_t *a_g
 int pgx_genome_sets_diff_dev(pgx_ctx *ctx, const uint64_t *d_a_bits, const uint64_t *d_b_bits, uint32_t n_rows,
                              uint32_t n_genomes, uint32_t *d_a_only, uint32_t *d_b_only, void *stream);
 
+/* The two device steps of the proximal (5'/3' UTR) pangenome builders (reference pangenome.py:900-1184).
+ *
+ * cut: text is text_bytes raw bytes; window i is the length[i] bytes at start[i], and its piece of the output is
+ * out[out_offsets[i] .. out_offsets[i] + length[i]), out_offsets being the exclusive prefix sum of the lengths (n + 1 entries).
+ *   reverse[i] == 0:  out[out_offsets[i] + k] = text[start[i] + k]; any byte is allowed, bad[i] = 0
+ *   reverse[i] != 0:  out[out_offsets[i] + k] = comp(text[start[i] + length[i] - 1 - k]), comp mapping
+ *                     ACGTWSRYMKNacgtwsrymkn to TGCAWSYRKMNtgcawsyrkmn; any other byte gives the output byte 0 and bad[i] = 1
+ * Zero-length windows are legal, windows may overlap or repeat, n = 0 does nothing. text_bytes >= 2^32 and n >= 2^24 fail
+ * with PGX_ERR_INVALID before anything is launched or written.
+ *   pgx_prox_cut      HOST pointers; computes the offsets itself (out holds the sum of the lengths, out_bad n bytes). A
+ *                     window that leaves [0, text_bytes) or an output of 2^32 bytes or more is refused the same way.
+ *   pgx_prox_cut_dev  the caller's DEVICE pointers (d_start and d_out_offsets 8-byte aligned, d_length 4-byte aligned; text
+ *                     and output may start at any address). One launch on `stream`, which is then synchronised; no
+ *                     workspace. The windows are not checked: every read is clamped into the text (a window is cut short at
+ *                     its end), and d_out must hold d_out_offsets[i] + length[i] bytes for every window.
+ * pgx_prox_cut_group_bytes(): the output bytes the lanes that share a window write per step.
+ *
+ * group: record i is the string i of a blob with n + 1 offsets (the conventions of pgx_dict_load) and a gene id
+ * 0 <= gene[i] < 2^24. Two records are equal iff they have the same gene, the same length and the same bytes.
+ *   first[i]    = the smallest j with record j equal to record i
+ *   variant[i]  = the number of j with first[j] == j, gene[j] == gene[i] and j < first[i]: the number a dictionary per gene
+ *                 gives a string when the records are entered in index order
+ *   *n_distinct = the number of i with first[i] == i
+ * All three are functions of the input alone: the same input gives the same bytes on every call. Hashes only decide where to
+ * look -- a j is reported after gene, length and bytes have been compared. PGX_PROX_NARROW_HASH (a test seam) keeps only the
+ * low 3 bits of every hash: same results, every probe collides. n >= 2^24, a blob of 2^32 bytes or more, decreasing offsets
+ * or a gene outside [0, 2^24) (host entry), unknown flags and too small a workspace fail with PGX_ERR_INVALID before anything
+ * is launched or written. n = 0 sets *n_distinct to 0.
+ *   pgx_prox_group      HOST pointers; the device buffers stay in the context between calls
+ *   pgx_prox_group_dev  the caller's DEVICE pointers (offsets 8-byte aligned, the int32 arrays 4-byte aligned) and workspace
+ *                       (pgx_prox_group_workspace_bytes(), 16-byte aligned; 0 for an n that is refused). Plain launches on
+ *                       `stream`, which is synchronised once at the end; inputs are not written, nothing outside the outputs
+ *                       and the workspace is. Offsets and genes are not checked: strings are clamped into [0, last offset)
+ *                       and only the low 24 bits of a gene order the records, so nothing outside the caller's buffers is
+ *                       touched, the result for broken input being unspecified.
+ * pgx_prox_group_tile(): the records one wave takes per pass of the sort by gene. */
+#define PGX_PROX_NARROW_HASH 1u   /* keep only the low 3 bits of every hash: same results, every probe collides */
+uint32_t pgx_prox_cut_group_bytes(void);
+uint32_t pgx_prox_group_tile(void);
+size_t pgx_prox_group_workspace_bytes(uint32_t n);
+int pgx_prox_cut(pgx_ctx *ctx, const uint8_t *text, uint64_t text_bytes, const uint64_t *start, const uint32_t *length,
+                 const uint8_t *reverse, uint32_t n, uint8_t *out, uint8_t *out_bad);
+int pgx_prox_cut_dev(pgx_ctx *ctx, const uint8_t *d_text, uint64_t text_bytes, const uint64_t *d_start,
+                     const uint32_t *d_length, const uint8_t *d_reverse, const uint64_t *d_out_offsets, uint32_t n,
+                     uint8_t *d_out, uint8_t *d_bad, void *stream);
+int pgx_prox_group(pgx_ctx *ctx, const uint8_t *blob, const uint64_t *offsets, const int32_t *gene, uint32_t n,
+                   uint32_t flags, int32_t *out_first, int32_t *out_variant, uint32_t *out_n_distinct);
+int pgx_prox_group_dev(pgx_ctx *ctx, const uint8_t *d_blob, const uint64_t *d_offsets, const int32_t *d_gene, uint32_t n,
+                       uint32_t flags, int32_t *d_first, int32_t *d_variant, uint32_t *d_n_distinct, void *d_workspace,
+                       size_t workspace_bytes, void *stream);
+
 /* feature names (pangenome.py:1944-1969) as fixed-width zero-padded ASCII records (numpy 'S<width>'):
  * <prefix><cluster>[<variant><member>]; variant NULL = gene names */
 int pgx_format_labels(const char *prefix, const char *variant, const int32_t *cluster, const int32_t *member,

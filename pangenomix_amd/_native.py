@@ -71,6 +71,7 @@ FCD_OVERLAP, FCD_DIM_BALANCE = 1, 2    # PGX_FCD_OVERLAP, PGX_FCD_DIM_BALANCE
 BERNOULLI_CD_LOGS = 1                  # PGX_BERNOULLI_CD_LOGS
 ASSOC_BLOCKS, ASSOC_DROP_EMPTY = 1, 2  # PGX_ASSOC_BLOCKS, PGX_ASSOC_DROP_EMPTY
 DICT_NARROW_HASH = 1                   # PGX_DICT_NARROW_HASH
+PROX_NARROW_HASH = 1                   # PGX_PROX_NARROW_HASH
 ASSOC_NARROW_HASH = 4                  # PGX_ASSOC_NARROW_HASH
 
 
@@ -192,6 +193,13 @@ SIGNATURES = {
     'pgx_dict_load': (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _P]),
     'pgx_dict_query': (C.c_int, [_P, _P, _P, C.c_uint32, _P]),
     'pgx_dict_match_dev': (C.c_int, [_P, _P, _P, C.c_uint32, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_size_t, _P]),
+    'pgx_prox_cut_group_bytes': (C.c_uint32, []),
+    'pgx_prox_group_tile': (C.c_uint32, []),
+    'pgx_prox_group_workspace_bytes': (C.c_size_t, [C.c_uint32]),
+    'pgx_prox_cut': (C.c_int, [_P, _P, C.c_uint64, _P, _P, _P, C.c_uint32, _P, _P]),
+    'pgx_prox_cut_dev': (C.c_int, [_P, _P, C.c_uint64, _P, _P, _P, _P, C.c_uint32, _P, _P, _P]),
+    'pgx_prox_group': (C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P]),
+    'pgx_prox_group_dev': (C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P, _P, C.c_size_t, _P]),
     'pgx_genome_sets_diff': (C.c_int, [_P, _P, _P, C.c_uint64, _P, _P, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P]),
     'pgx_genome_sets_diff_dev': (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P]),
     'pgx_cluster_greedy': (C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(ClusterParams), _P, _P, _P, _P,
@@ -998,6 +1006,56 @@ class Context(object):
         """The same on device bitmaps (raw device addresses; synchronises `stream`, see pgx.h)."""
         check(lib().pgx_genome_sets_diff_dev(self._h, d_a_bits, d_b_bits, int(n_rows), int(n_genomes), d_a_only, d_b_only,
                                              stream))
+
+    # -- windows of a text, records grouped per gene (pangenome.build_proximal_pangenome) ------------------------------------
+    def prox_cut(self, text, start, length, reverse):
+        """(out, out_offsets, bad): window i -- the length[i] bytes of `text` (bytes or a 1-D uint8 array) at start[i],
+        reverse-complemented where reverse[i] is set -- is out[out_offsets[i]:out_offsets[i + 1]]; bad[i] = 1 where a reverse
+        window holds a byte without a complement, which comes out as 0 (pgx.h: pgx_prox_cut)."""
+        if isinstance(text, (bytes, bytearray, memoryview)):
+            text = np.frombuffer(text, dtype=np.uint8)
+        text = np.ascontiguousarray(text, dtype=np.uint8)
+        start = np.ascontiguousarray(start, dtype=np.uint64)
+        length = np.ascontiguousarray(length, dtype=np.uint32)
+        reverse = np.ascontiguousarray(reverse, dtype=np.uint8)
+        if text.ndim != 1 or start.ndim != 1 or start.shape != length.shape or start.shape != reverse.shape:
+            raise ValueError('text must be 1-D and start, length, reverse 1-D arrays of one length')
+        out_offsets = np.zeros(start.size + 1, dtype=np.uint64)
+        np.cumsum(length, dtype=np.uint64, out=out_offsets[1:])
+        out = np.zeros(min(int(out_offsets[-1]), (1 << 32) - 1), dtype=np.uint8)     # (a larger one is refused)
+        bad = np.zeros(start.size, dtype=np.uint8)
+        check(lib().pgx_prox_cut(self._h, _ptr(text), text.size, _ptr(start), _ptr(length), _ptr(reverse), start.size,
+                                 _ptr(out), _ptr(bad)))
+        return out, out_offsets, bad
+
+    def prox_cut_dev(self, d_text, text_bytes, d_start, d_length, d_reverse, d_out_offsets, n, d_out, d_bad, stream=0):
+        """The same on device memory (raw device addresses; synchronises `stream`, see pgx.h)."""
+        check(lib().pgx_prox_cut_dev(self._h, d_text, int(text_bytes), d_start, d_length, d_reverse, d_out_offsets, int(n),
+                                     d_out, d_bad, stream))
+
+    def prox_group(self, blob, offsets, gene, flags=0):
+        """(first, variant, n_distinct) of the records blob[offsets[i]:offsets[i + 1]] keyed by gene[i]: the smallest
+        index of an equal record, and the number of distinct records of the gene that appear before it (pgx.h:
+        pgx_prox_group). flags: PROX_NARROW_HASH, the test seam."""
+        blob, offsets = self._string_args(blob, offsets)
+        gene = np.ascontiguousarray(gene, dtype=np.int32)
+        if gene.ndim != 1 or gene.size != offsets.size - 1:
+            raise ValueError('gene must hold one entry per record')
+        first = np.zeros(gene.size, dtype=np.int32)
+        variant = np.zeros(gene.size, dtype=np.int32)
+        distinct = C.c_uint32(0)
+        check(lib().pgx_prox_group(self._h, _ptr(blob), _ptr(offsets), _ptr(gene), gene.size, int(flags), _ptr(first),
+                                   _ptr(variant), C.byref(distinct)))
+        return first, variant, int(distinct.value)
+
+    def prox_group_workspace_bytes(self, n):
+        return int(lib().pgx_prox_group_workspace_bytes(int(n)))
+
+    def prox_group_dev(self, d_blob, d_offsets, d_gene, n, d_first, d_variant, d_n_distinct, d_ws, ws_bytes, flags=0,
+                       stream=0):
+        """The same on device memory (raw device addresses; synchronises `stream`, see pgx.h)."""
+        check(lib().pgx_prox_group_dev(self._h, d_blob, d_offsets, d_gene, int(n), int(flags), d_first, d_variant,
+                                       d_n_distinct, d_ws, int(ws_bytes), stream))
 
     def pan_core(self, bits, n_genes, perms):
         perms = np.ascontiguousarray(perms, dtype=np.int32)

@@ -68,6 +68,9 @@ enum DevSlot : int {        // pgx_ctx::arena, through DevBuf
     SD_SLOT_ROWS, SD_SLOT_GENOMES, SD_SLOT_A_BITS, SD_SLOT_A_CNT, SD_SLOT_B_BITS, SD_SLOT_B_CNT, SD_SLOT_OUT,
     // svm.hip: the table, the workspace (Gram matrices, status), every uploaded input in one, every result in one
     SV_SLOT_BITS, SV_SLOT_ROWS, SV_SLOT_GENOMES, SV_SLOT_CNT, SV_SLOT_WS, SV_SLOT_IN, SV_SLOT_OUT,
+    // prox.hip: pgx_prox_cut (the text, the window arrays in one, output and bad flags in one), then pgx_prox_group (the
+    // blob, offsets and genes in one, the workspace, every result in one)
+    PX_SLOT_TEXT, PX_SLOT_WINDOWS, PX_SLOT_OUT, PX_SLOT_BLOB, PX_SLOT_RECORDS, PX_SLOT_WS, PX_SLOT_RESULT,
     DEV_SLOT_COUNT
 };
 enum HostSlot : int {       // pgx_ctx::host_scratch, through HostVec
@@ -81,6 +84,7 @@ enum HostSlot : int {       // pgx_ctx::host_scratch, through HostVec
     RN_HOST_STATUS,
     CS_HOST_STATUS,
     SV_HOST_STATUS,
+    PX_HOST_OFFSETS,
     HOST_SLOT_COUNT
 };
 enum PinSlot : int {        // pgx_ctx::host_arena, through Pinned (cluster.hip)

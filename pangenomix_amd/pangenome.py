@@ -24,6 +24,7 @@ unknown `cdhit_args` keys are rejected instead of silently passed through.
 """
 
 from __future__ import print_function
+import collections
 import os
 import hashlib
 import subprocess as sp
@@ -726,13 +727,18 @@ def __load_feature_to_allele__(allele_names):
 
 
 def extract_proximal_sequences(genome_gff, genome_fna, proximal_out, limits, max_overlap, side,
-                               feature_to_allele=None, allele_names=None, include_fragments=False):
+                               feature_to_allele=None, allele_names=None, include_fragments=False, ctx=None):
     """Nucleotides upstream / downstream of every mapped GFF feature (PATRIC flavour: contig column
     'accn|<contig>', ID attribute) written as '<ID>_<side>(<limits>[,<max_overlap>])' records
     (reference :1038-1184). limits = (-X, Y): upstream X bases before the start codon + the first Y coding
     bases; downstream the last X coding bases + Y bases after the stop. max_overlap >= 0 truncates a region
     that runs into the neighbouring CDS on the same strand (GFF order). Regions cut off by a contig end are
-    dropped unless include_fragments."""
+    dropped unless include_fragments. ctx (a _native.Context): the windows are cut on the device (csrc/prox.hip,
+    DESIGN.md 6k), the file is the same bytes; a genome that is not regular goes through the code below."""
+    if ctx is not None:
+        _extract_proximal_with_ctx(ctx, genome_gff, genome_fna, proximal_out, limits, max_overlap, side,
+                                   feature_to_allele, allele_names, include_fragments)
+        return
     neighbours = {}      # contig -> strand -> (start, stop) -> (end of the CDS before, start of the CDS after)
     if max_overlap >= 0:
         placed = {}
@@ -803,25 +809,29 @@ def extract_proximal_sequences(genome_gff, genome_fna, proximal_out, limits, max
 
 
 def extract_upstream_sequences(genome_gff, genome_fna, upstream_out, limits=(-50, 3), max_overlap=-1,
-                               feature_to_allele=None, allele_names=None, include_fragments=False):
+                               feature_to_allele=None, allele_names=None, include_fragments=False, ctx=None):
     """Reference :1021-1029."""
     extract_proximal_sequences(genome_gff, genome_fna, proximal_out=upstream_out, limits=limits, max_overlap=max_overlap,
                                side='upstream', feature_to_allele=feature_to_allele, allele_names=allele_names,
-                               include_fragments=include_fragments)
+                               include_fragments=include_fragments, ctx=ctx)
 
 
 def extract_downstream_sequences(genome_gff, genome_fna, downstream_out, limits=(-3, 50), max_overlap=-1,
-                                 feature_to_allele=None, allele_names=None, include_fragments=False):
+                                 feature_to_allele=None, allele_names=None, include_fragments=False, ctx=None):
     """Reference :1032-1040."""
     extract_proximal_sequences(genome_gff, genome_fna, proximal_out=downstream_out, limits=limits, max_overlap=max_overlap,
                                side='downstream', feature_to_allele=feature_to_allele, allele_names=allele_names,
-                               include_fragments=include_fragments)
+                               include_fragments=include_fragments, ctx=ctx)
 
 
-def consolidate_proximal(genome_proximals, nr_proximal_out, feature_to_allele, side, output_format='lsdf'):
+def consolidate_proximal(genome_proximals, nr_proximal_out, feature_to_allele, side, output_format='lsdf', ctx=None):
     """Non-redundant proximal sequences PER GENE (<name>_C#U# upstream, <name>_C#D# downstream; the number
     is the order of first appearance within the gene) and the proximal x genome table (reference :900-1018).
-    Files are taken in sorted order; the genome is the file name up to '_<side>'."""
+    Files are taken in sorted order; the genome is the file name up to '_<side>'. ctx (a _native.Context): the records
+    are grouped and numbered on the device (csrc/prox.hip), files and table are the same; a call that is
+    not regular goes through the code below."""
+    if ctx is not None:
+        return _consolidate_proximal_with_ctx(ctx, genome_proximals, nr_proximal_out, feature_to_allele, side, output_format, {})
     letter = VARIANT_TYPES[side]
     variants = {}        # gene -> {sequence: number}
     per_genome = {}      # genome -> {proximal id: 1}, insertion order = first appearance
@@ -871,15 +881,17 @@ def consolidate_proximal(genome_proximals, nr_proximal_out, feature_to_allele, s
 
 def build_proximal_pangenome(genome_data, allele_names, output_dir, limits, side, name='Test',
                              include_fragments=False, max_overlap=-1, fastasort_path=None,
-                             output_format='lsdf', fna_output_footer='', overwrite_extract=False):
+                             output_format='lsdf', fna_output_footer='', overwrite_extract=False, ctx=None):
     """Proximal-region pangenome relative to the gene clusters of build_cds_pangenome(): per genome
     `<gffdir>/derived/<genome>_<side><footer>.fna`, then `<name>_nr_<side>.fna` and
-    `<name>_strain_by_<side>.npz` (reference :777-897)."""
+    `<name>_strain_by_<side>.npz` (reference :777-897). ctx (a _native.Context): windows are cut and records grouped
+    on the device, and the records of a genome just extracted there are grouped from memory."""
     output_format = _check_format(output_format)
     print('Loading header-allele mapping...')
     feature_to_allele = __load_feature_to_allele__(allele_names)
     print('Extracting', side, 'sequences...')
     genome_proximals = []
+    extracted = {}       # ctx: extract path -> the records of a genome just extracted on the device
     for i, (gff, fna) in enumerate(genome_data):
         genome = __get_genome_from_filename__(gff)
         gdir = '/'.join(gff.split('/')[:-1]) + '/' if '/' in gff else ''
@@ -892,11 +904,22 @@ def build_proximal_pangenome(genome_data, allele_names, output_dir, limits, side
             print(i + 1, 'Using pre-existing', side, 'regions for', genome)
         else:
             print(i + 1, 'Extracting', side, 'regions for', genome)
+            if ctx is not None:
+                extracted.pop(prox, None)
+                records = _extract_proximal_with_ctx(ctx, gff, fna, prox, limits, max_overlap, side, feature_to_allele, None,
+                                                     include_fragments)
+                if records is not None:
+                    extracted[prox] = records
+                continue
             extract_proximal_sequences(gff, fna, prox, limits=limits, side=side, feature_to_allele=feature_to_allele,
                                        include_fragments=include_fragments, max_overlap=max_overlap)
     print('Identifying non-redundant', side, 'sequences per gene...')
     nr_out = _p(output_dir, name, '_nr_' + side + '.fna')
-    df_proximal = consolidate_proximal(genome_proximals, nr_out, feature_to_allele, side, output_format=output_format)
+    if ctx is not None:
+        df_proximal = _consolidate_proximal_with_ctx(ctx, genome_proximals, nr_out, feature_to_allele, side, output_format,
+                                                     extracted)
+    else:
+        df_proximal = consolidate_proximal(genome_proximals, nr_out, feature_to_allele, side, output_format=output_format)
     if fastasort_path:
         print('Sorting sequences by header...')
         with open(nr_out + '.tmp', 'w+') as f_sort:
@@ -910,22 +933,440 @@ def build_proximal_pangenome(genome_data, allele_names, output_dir, limits, side
 
 def build_upstream_pangenome(genome_data, allele_names, output_dir, limits=(-50, 3), name='Test',
                              include_fragments=False, max_overlap=-1, fastasort_path=None, output_format='lsdf',
-                             fna_output_footer='', overwrite_extract=False):
+                             fna_output_footer='', overwrite_extract=False, ctx=None):
     """5'UTR pangenome (reference :743-757)."""
     return build_proximal_pangenome(genome_data, allele_names, output_dir, limits, side='upstream', name=name,
                                     include_fragments=include_fragments, max_overlap=max_overlap,
                                     fastasort_path=fastasort_path, output_format=output_format,
-                                    fna_output_footer=fna_output_footer, overwrite_extract=overwrite_extract)
+                                    fna_output_footer=fna_output_footer, overwrite_extract=overwrite_extract, ctx=ctx)
 
 
 def build_downstream_pangenome(genome_data, allele_names, output_dir, limits=(-3, 50), name='Test',
                                include_fragments=False, max_overlap=-1, fastasort_path=None, output_format='lsdf',
-                               fna_output_footer='', overwrite_extract=False):
+                               fna_output_footer='', overwrite_extract=False, ctx=None):
     """3'UTR pangenome (reference :761-775)."""
     return build_proximal_pangenome(genome_data, allele_names, output_dir, limits, side='downstream', name=name,
                                     include_fragments=include_fragments, max_overlap=max_overlap,
                                     fastasort_path=fastasort_path, output_format=output_format,
-                                    fna_output_footer=fna_output_footer, overwrite_extract=overwrite_extract)
+                                    fna_output_footer=fna_output_footer, overwrite_extract=overwrite_extract, ctx=ctx)
+
+
+# ---------------------------------------------------------------------------
+# the same builders with ctx=: windows cut and records grouped on the device (csrc/prox.hip, DESIGN.md 6k). Everything
+# here works on whole files as byte arrays -- no statement runs per GFF line, per record or per base (a file's contigs, the
+# files and the distinct alleles are looped over). Only REGULAR input is handled: for anything else a function returns None
+# before it has written or printed anything, and its caller runs the host function above, called exactly as without ctx,
+# so that what an odd input gives -- exceptions and partial files included -- is the host path's by construction.
+# ---------------------------------------------------------------------------
+PROXIMAL_PATH_COUNTS = collections.Counter()    # extract_device / extract_host per genome, consolidate_device / _host per call
+_PROX_MAX_RECORDS, _PROX_MAX_BYTES, _PROX_MAX_GENES = 1 << 24, 1 << 32, 1 << 24     # the limits of pgx_prox_cut / _group
+_PROX_SPACE = np.zeros(256, dtype=bool)
+_PROX_SPACE[[9, 11, 12, 32]] = True             # what strip() takes off a line of a regular file ('\n' ends it, '\r' is irregular)
+
+
+def _plain_ascii(data):
+    """the rule of _fasta_records, and no NUL (fixed-width numpy strings end at one)"""
+    return data.isascii() and data.translate(None, _STR_ONLY_SPACE + b'\x00') == data
+
+
+def _line_spans(arr):
+    """(starts, ends) of the lines of a byte array, the '\n' excluded; a last line without one counts"""
+    nl = np.flatnonzero(arr == 10)
+    starts = np.concatenate((np.zeros(1, dtype=np.int64), nl + 1))
+    ends = np.concatenate((nl, np.array([arr.size], dtype=np.int64)))
+    if starts[-1] == arr.size:
+        starts, ends = starts[:-1], ends[:-1]
+    return starts, ends
+
+
+def _ragged_index(starts, lens):
+    """the indices starts[0] .. starts[0] + lens[0] - 1, starts[1] .., end to end"""
+    lens = np.asarray(lens, dtype=np.int64)
+    before = np.cumsum(lens) - lens
+    return np.repeat(np.asarray(starts, dtype=np.int64) - before, lens) + np.arange(int(lens.sum()), dtype=np.int64)
+
+
+def _fixed_width(arr, starts, lens):
+    """the byte strings arr[starts[i]:starts[i] + lens[i]] as one numpy 'S' array"""
+    width = max(int(lens.max()) if lens.size else 0, 1)
+    out = np.zeros((lens.size, width), dtype=np.uint8)
+    if lens.size:
+        rows = np.repeat(np.arange(lens.size, dtype=np.int64), lens)
+        out[rows, _ragged_index(np.zeros(lens.size, dtype=np.int64), lens)] = arr[_ragged_index(starts, lens)]
+    return out.view('S%d' % width).reshape(-1)
+
+
+def _decimal_fields(arr, starts, ends):
+    """int64 values of fields of plain decimal digits; None if one of them is anything else"""
+    lens = ends - starts
+    if lens.size == 0:
+        return np.zeros(0, dtype=np.int64)
+    if int(lens.min()) < 1 or int(lens.max()) > 18:
+        return None
+    digits = arr[_ragged_index(starts, lens)].astype(np.int64) - 48
+    if digits.min() < 0 or digits.max() > 9:
+        return None
+    place = np.repeat(lens, lens) - 1 - _ragged_index(np.zeros(lens.size, dtype=np.int64), lens)
+    return np.add.reduceat(digits * 10 ** place, np.cumsum(lens) - lens)
+
+
+def _parse_gff_regular(data):
+    """The non-comment lines of a GFF file as arrays (one entry per line, file order), or None if the file is not regular:
+    arr (the file's bytes), contig (start, end of the name behind the last '|'), is_cds, start0, stop, plus, id (start, end
+    of the value of the last ID attribute)."""
+    if not _plain_ascii(data):
+        return None
+    arr = np.frombuffer(data, dtype=np.uint8)
+    ls, le = _line_spans(arr)
+    full = le > ls
+    ls, le = ls[full], le[full]
+    if ls.size and (_PROX_SPACE[arr[ls]].any() or _PROX_SPACE[arr[le - 1]].any()):
+        return None                                          # (strip() would change the line: leave it to the host)
+    keep = arr[ls] != 35 if ls.size else np.zeros(0, dtype=bool)                     # '#'
+    ls, le = ls[keep], le[keep]
+    n = ls.size
+    tabs = np.flatnonzero(arr == 9)
+    lo = np.searchsorted(tabs, ls)
+    if n and (np.searchsorted(tabs, le) - lo != 8).any():
+        return None
+    t = tabs[lo[:, None] + np.arange(8)[None, :]] if n else np.zeros((0, 8), dtype=np.int64)
+    # contig.split('|')[-1]
+    pipes = np.flatnonzero(arr == 124)
+    c_end = t[:, 0]
+    c_start = ls.copy()
+    if pipes.size and n:
+        j = np.searchsorted(pipes, c_end) - 1
+        last = pipes[np.maximum(j, 0)]
+        c_start = np.where((j >= 0) & (last >= ls), last + 1, ls)
+    ty = t[:, 1] + 1
+    at = lambda p: arr[np.minimum(p, arr.size - 1)]                                   # noqa: E731
+    is_cds = (t[:, 2] - ty == 3) & (at(ty) == 67) & (at(ty + 1) == 68) & (at(ty + 2) == 83)
+    start = _decimal_fields(arr, t[:, 2] + 1, t[:, 3])
+    stop = _decimal_fields(arr, t[:, 3] + 1, t[:, 4])
+    if start is None or stop is None:
+        return None
+    strand = at(t[:, 5] + 1)
+    if n and ((t[:, 6] - t[:, 5] != 2).any() or ((strand != 43) & (strand != 45)).any()):
+        return None
+    # the attributes: entries between ';', each with exactly one '=' -- the separators of a line alternate '=', ';', ..., '='
+    a_start = t[:, 7] + 1
+    seps = np.flatnonzero((arr == 59) | (arr == 61))
+    s_lo = np.searchsorted(seps, a_start)
+    count = np.searchsorted(seps, le) - s_lo
+    if n and (count % 2 != 1).any():
+        return None
+    sp = seps[_ragged_index(s_lo, count)]
+    line = np.repeat(np.arange(n, dtype=np.int64), count)
+    k = _ragged_index(np.zeros(n, dtype=np.int64), count)
+    if sp.size and (arr[sp] != np.where(k % 2 == 0, 61, 59)).any():
+        return None
+    is_eq = k % 2 == 0
+    before = np.concatenate((np.zeros(1, dtype=np.int64), sp[:-1])) if sp.size else sp
+    after = np.concatenate((sp[1:], np.zeros(1, dtype=np.int64))) if sp.size else sp
+    entry_start = np.where(k == 0, a_start[line], before + 1)[is_eq]
+    value_end = np.where(k == count[line] - 1, le[line], after)[is_eq]
+    eq, line = sp[is_eq], line[is_eq]
+    is_id = (eq - entry_start == 2) & (at(entry_start) == 73) & (at(entry_start + 1) == 68)
+    eq, value_end, line = eq[is_id], value_end[is_id], line[is_id]
+    last_of_line = np.ones(line.size, dtype=bool)
+    last_of_line[:-1] = line[1:] != line[:-1]                # a later ID entry replaces an earlier one
+    if int(last_of_line.sum()) != n:
+        return None                                          # a line without ID
+    return dict(arr=arr, n=n, contig=(c_start, c_end), is_cds=is_cds, start0=start - 1, stop=stop, plus=strand == 43,
+                id=(eq[last_of_line] + 1, value_end[last_of_line]))
+
+
+def _parse_fna_regular(data):
+    """(text uint8: the contigs end to end, {name: (offset, length)}) as load_sequences_from_fasta(header_fxn=first token)
+    gives them, or None if the file is not regular. The loop is over contigs."""
+    if not data.isascii() or (data and data[:1] != b'>'):
+        return None
+    # one pass over the file: bytes that make it irregular anywhere, and blanks, which may stand in header lines only
+    odd = _STR_ONLY_SPACE + b'\x00'
+    outside_lines = len(data) - len(data.translate(None, odd + _BYTES_SPACE))
+    pieces, where, total = [], {}, 0
+    for i, chunk in enumerate(data.split(b'\n>') if data else ()):
+        head, _, body = chunk.partition(b'\n')
+        if i == 0:
+            head = head[1:]                                  # (the file's first '>')
+        tokens = head.split()
+        if not tokens:
+            return None                                      # (no name: IndexError on the host)
+        if len(head.translate(None, odd)) != len(head):
+            return None
+        outside_lines -= len(head) - len(head.translate(None, _BYTES_SPACE))
+        seq = body.replace(b'\n', b'')
+        if seq:
+            where[tokens[0]] = (total, len(seq))             # a later contig of the same name replaces the earlier one
+            pieces.append(seq)
+            total += len(seq)
+    if outside_lines:
+        return None                                          # (blanks inside a sequence line: strip() would leave them there)
+    return np.frombuffer(b''.join(pieces), dtype=np.uint8), where
+
+
+def _parse_extract_regular(data, side):
+    """The records of a per-genome extract as consolidate_proximal takes them -- (features: list of str, blob uint8: the
+    sequences end to end, lengths int64) -- or None if the file is not regular (an empty one is not). A record without a
+    sequence is dropped unless it is the file's last; lines before the first header are a record with the feature ''."""
+    if not data or not _plain_ascii(data):
+        return None
+    arr = np.frombuffer(data, dtype=np.uint8)
+    ls, le = _line_spans(arr)
+    full = le > ls
+    first = np.where(full, arr[np.minimum(ls, arr.size - 1)], 10)
+    last = np.where(full, arr[np.maximum(le, 1) - 1], 10)
+    is_header = first == 62
+    if ((_PROX_SPACE[first] | _PROX_SPACE[last]) & ~is_header).any():
+        return None                                          # (strip() would change a sequence line: leave it to the host)
+    record = np.cumsum(is_header)
+    n_records = int(record[-1]) + 1 if record.size else 1
+    seq_lines = ~is_header
+    lengths = np.bincount(record[seq_lines], weights=(le - ls)[seq_lines], minlength=n_records).astype(np.int64)
+    keep = lengths > 0
+    keep[-1] = True                                          # the last record, unconditionally
+    blob = arr[_ragged_index(ls[seq_lines], (le - ls)[seq_lines])]
+    heads = np.char.strip(_fixed_width(arr, ls[is_header] + 1, (le - ls)[is_header] - 1))
+    features = np.concatenate((np.array([b''], dtype=heads.dtype), np.char.partition(heads, ('_' + side + '(').encode())[:, 0])) \
+        if heads.size else np.array([b''], dtype='S1')
+    return list(map(bytes.decode, features[keep].tolist())), blob, lengths[keep]
+
+
+def _proximal_neighbours(g, contig_names, wanted):
+    """For the lines `wanted` (indices) of a parsed GFF: (left, has_left, right, has_right) of the CDS that has the line's
+    contig, strand, start and stop -- the end of the CDS before it and the start of the one after it on that contig and
+    strand, in file order -- or None where the host's dictionaries would not give that (two CDS with one key, no CDS)."""
+    _, contig_id = np.unique(contig_names, return_inverse=True)
+    group = contig_id.reshape(-1).astype(np.int64) * 2 + g['plus']
+    cds = np.flatnonzero(g['is_cds'])
+    keys = np.stack((group, g['start0'], g['stop']), axis=1)
+    uniq, inverse = np.unique(keys, axis=0, return_inverse=True)
+    inverse = inverse.reshape(-1)
+    per_key = np.bincount(inverse[cds], minlength=uniq.shape[0])
+    if (per_key > 1).any() or (per_key[inverse[wanted]] == 0).any():
+        return None
+    order = np.argsort(group[cds], kind='stable')
+    grp, start0, stop = group[cds][order], g['start0'][cds][order], g['stop'][cds][order]
+    same_as_before = np.zeros(cds.size, dtype=bool)
+    same_as_before[1:] = grp[1:] == grp[:-1]
+    same_as_next = np.zeros(cds.size, dtype=bool)
+    same_as_next[:-1] = same_as_before[1:]
+    position = np.empty(cds.size, dtype=np.int64)            # of a CDS (by its place among the CDS lines) in `order`
+    position[order] = np.arange(cds.size)
+    cds_of_key = np.zeros(uniq.shape[0], dtype=np.int64)
+    cds_of_key[inverse[cds]] = np.arange(cds.size)
+    at = position[cds_of_key[inverse[wanted]]]
+    return (stop[np.maximum(at - 1, 0)], same_as_before[at], start0[np.minimum(at + 1, max(cds.size - 1, 0))], same_as_next[at])
+
+
+def _extract_proximal_device(ctx, genome_gff, genome_fna, proximal_out, limits, max_overlap, side, feat_to_allele,
+                             include_fragments):
+    """extract_proximal_sequences for a regular genome: writes the file, prints the count, returns the file's bytes. None
+    (nothing written or printed) for a genome that is left to the host."""
+    import itertools
+    import numbers
+    from . import _native
+    if feat_to_allele is None or side not in ('upstream', 'downstream') or len(limits) != 2:
+        return None
+    if not all(isinstance(x, numbers.Integral) and abs(int(x)) < 1 << 40 for x in (limits[0], limits[1], max_overlap)):
+        return None
+    try:
+        with open(genome_gff, 'rb') as f:
+            gff_data = f.read()
+        with open(genome_fna, 'rb') as f:
+            fna_data = f.read()
+    except OSError:
+        return None
+    g = _parse_gff_regular(gff_data)
+    contigs = _parse_fna_regular(fna_data) if g is not None else None
+    if contigs is None:
+        return None
+    text, where = contigs
+    arr, n = g['arr'], g['n']
+    params = (limits[0], limits[1], max_overlap) if max_overlap >= 0 else limits
+    footer = '_' + side + str(params).replace(' ', '')
+    if not footer.isascii():
+        return None
+    coding_length = limits[1] if side == 'upstream' else -limits[0]
+    contig_names = _fixed_width(arr, g['contig'][0], g['contig'][1] - g['contig'][0])
+    id_start, id_len = g['id'][0], g['id'][1] - g['id'][0]
+    contig_of = np.fromiter(map({name: i for i, name in enumerate(where)}.get, contig_names.tolist(), itertools.repeat(-1)),
+                            dtype=np.int64, count=n)
+    ids = list(map(bytes.decode, _fixed_width(arr, id_start, id_len).tolist()))
+    mapped = np.fromiter(map(feat_to_allele.__contains__, ids), dtype=bool, count=n)
+    wanted = np.flatnonzero((contig_of >= 0) & mapped)
+    spans = np.array(list(where.values()), dtype=np.int64).reshape(-1, 2)
+    contig_off, contig_len = spans[contig_of[wanted], 0], spans[contig_of[wanted], 1]
+    plus, start0, stop = g['plus'][wanted], g['start0'][wanted], g['stop'][wanted]
+    anchor = np.where(plus == (side == 'upstream'), start0, stop)
+    utr_start = anchor + np.where(plus, limits[0], -limits[1])
+    utr_stop = anchor + np.where(plus, limits[1], -limits[0])
+    if max_overlap >= 0:
+        around = _proximal_neighbours(g, contig_names, wanted)
+        if around is None:
+            return None
+        left, has_left, right, has_right = around
+        utr_start = np.where(has_left & (utr_start < left - max_overlap), left - max_overlap, utr_start)
+        utr_stop = np.where(has_right & (utr_stop > right + max_overlap), right + max_overlap, utr_stop)
+    # seq[utr_start:utr_stop] as Python slices it: a negative index counts from the end, both are clipped into the contig
+    lo = np.where(utr_start < 0, np.maximum(utr_start + contig_len, 0), np.minimum(utr_start, contig_len))
+    hi = np.where(utr_stop < 0, np.maximum(utr_stop + contig_len, 0), np.minimum(utr_stop, contig_len))
+    length = np.maximum(hi - lo, 0)
+    is_fragment = (utr_start < 0) | (utr_stop > contig_len)
+    written = (length > coding_length) & (~is_fragment | bool(include_fragments))
+    cut = written | ~plus                                    # (a minus window that is not written is still checked)
+    if int(cut.sum()) >= _PROX_MAX_RECORDS or text.size >= _PROX_MAX_BYTES or int(length[cut].sum()) >= _PROX_MAX_BYTES:
+        return None
+    try:
+        out, out_offsets, bad = ctx.prox_cut(text, (contig_off + lo)[cut], length[cut], ~plus[cut])
+    except _native.PgxError as e:
+        if getattr(e, 'status', None) != -1:
+            raise
+        return None                                          # beyond the library's limits
+    if bad.any():
+        return None                                          # the host raises its KeyError at that record
+    keep = written[cut]
+    seq_start, seq_len = out_offsets[:-1].astype(np.int64)[keep], length[cut][keep]
+    id_start, id_len = id_start[wanted][written], id_len[wanted][written]
+    foot = np.frombuffer(footer.encode('ascii'), dtype=np.uint8)
+    record_len = 1 + id_len + foot.size + 1 + seq_len + 1
+    at = np.cumsum(record_len) - record_len
+    image = np.full(int(record_len.sum()), 10, dtype=np.uint8)                       # ('\n' where nothing else goes)
+    image[at] = 62
+    image[_ragged_index(at + 1, id_len)] = arr[_ragged_index(id_start, id_len)]
+    image[(at + 1 + id_len)[:, None] + np.arange(foot.size)[None, :]] = foot[None, :]
+    image[_ragged_index(at + 1 + id_len + foot.size + 1, seq_len)] = out[_ragged_index(seq_start, seq_len)]
+    image = image.tobytes()
+    with open(proximal_out, 'wb') as f:
+        f.write(image)
+    print('Loaded', side, 'sequences:', int(written.sum()))
+    return image
+
+
+def _extract_proximal_with_ctx(ctx, genome_gff, genome_fna, proximal_out, limits, max_overlap, side, feature_to_allele,
+                               allele_names, include_fragments):
+    """One genome of extract_proximal_sequences(ctx=...). Returns the records of the file written, as
+    _parse_extract_regular gives them, when they came from the device, else None."""
+    feat_to_allele = None
+    if feature_to_allele:
+        feat_to_allele = feature_to_allele
+    elif allele_names:
+        feat_to_allele = __load_feature_to_allele__(allele_names)
+    image = _extract_proximal_device(ctx, genome_gff, genome_fna, proximal_out, limits, max_overlap, side, feat_to_allele,
+                                     include_fragments)
+    if image is None:
+        PROXIMAL_PATH_COUNTS['extract_host'] += 1
+        extract_proximal_sequences(genome_gff, genome_fna, proximal_out, limits=limits, max_overlap=max_overlap, side=side,
+                                   feature_to_allele=feature_to_allele, allele_names=allele_names,
+                                   include_fragments=include_fragments)
+        return None
+    PROXIMAL_PATH_COUNTS['extract_device'] += 1
+    return _parse_extract_regular(image, side)               # (what re-reading the file would give; None: re-read it)
+
+
+def _proximal_row_order(gene_names, genes, variants, letter):
+    """(names, rank): the ids <gene><letter><variant> and the place of each among them sorted as strings"""
+    from . import _native
+    used = np.unique(genes)
+    parts = [gene_names[int(g)].rpartition('C') for g in used]
+    prefixes = {p[0] + p[1] for p in parts}
+    if len(prefixes) == 1 and all(p[1] and p[2].isascii() and p[2].isdigit() and str(int(p[2])) == p[2] and int(p[2]) < 1 << 31
+                                  for p in parts) and next(iter(prefixes)).isascii():
+        cluster_of = np.zeros(int(used.max()) + 1 if used.size else 1, dtype=np.int32)
+        cluster_of[used] = [int(p[2]) for p in parts]
+        names = _native.format_labels(next(iter(prefixes)), cluster_of[genes], variants, letter)
+        order = _native.allele_order(cluster_of[genes], variants)
+    else:
+        names = np.array([gene_names[int(g)] + letter + str(int(v)) for g, v in zip(genes, variants)], dtype=object)
+        order = np.array(sorted(range(names.size), key=names.__getitem__), dtype=np.int64)
+    rank = np.empty(names.size, dtype=np.int64)
+    rank[order] = np.arange(names.size)
+    return names, rank
+
+
+def _consolidate_proximal_device(ctx, genome_proximals, nr_proximal_out, feature_to_allele, side, extracted):
+    """consolidate_proximal for a regular call; None (nothing written or printed) for one that is left to the host"""
+    import itertools
+    from . import _native
+    letter = VARIANT_TYPES[side]
+    paths = sorted(genome_proximals)
+    genome_order = [path.split('/')[-1].split('_' + side)[0] for path in paths]
+    if len(set(genome_order)) != len(genome_order):
+        return None
+    features, blobs, lengths, per_file = [], [], [], []
+    for path in paths:
+        records = extracted.get(path)
+        if records is None:
+            try:
+                with open(path, 'rb') as f:
+                    records = _parse_extract_regular(f.read(), side)
+            except OSError:
+                return None
+            if records is None:
+                return None
+        features.extend(records[0])
+        blobs.append(records[1])
+        lengths.append(records[2])
+        per_file.append(len(records[0]))
+    gene_names, gene_ids, gene_of_allele = [], {}, {}
+    for allele in set(feature_to_allele.values()):           # once per distinct allele
+        gene = __get_gene_from_allele__(allele)
+        if gene not in gene_ids:
+            gene_ids[gene] = len(gene_names)
+            gene_names.append(gene)
+        gene_of_allele[allele] = gene_ids[gene]
+    n = len(features)
+    genes = np.fromiter(map(gene_of_allele.get, map(feature_to_allele.get, features), itertools.repeat(-1)), dtype=np.int64,
+                        count=n)
+    if n == 0 or genes.min() < 0:
+        return None                                          # a feature without an allele: KeyError on the host
+    blob = np.concatenate(blobs)
+    offsets = np.zeros(n + 1, dtype=np.uint64)
+    np.cumsum(np.concatenate(lengths), out=offsets[1:])
+    if n >= _PROX_MAX_RECORDS or blob.size >= _PROX_MAX_BYTES or len(gene_names) >= _PROX_MAX_GENES:
+        return None
+    if not ''.join(gene_names).isascii():
+        return None                                          # (the file is put together as bytes)
+    try:
+        first, variant, n_distinct = ctx.prox_group(blob, offsets, genes.astype(np.int32))
+    except _native.PgxError as e:
+        if getattr(e, 'status', None) != -1:
+            raise
+        return None                                          # beyond the library's limits
+    own = first == np.arange(n)
+    distinct = np.flatnonzero(own)                           # the records written, in the order they are met
+    names, rank = _proximal_row_order(gene_names, genes[distinct], variant[distinct], letter)
+    names_s = np.asarray(names).astype('S')
+    name_len = np.char.str_len(names_s).astype(np.int64)
+    seq_start, seq_len = offsets[:-1].astype(np.int64)[distinct], np.concatenate(lengths)[distinct]
+    record_len = 1 + name_len + 1 + seq_len + 1
+    at = np.cumsum(record_len) - record_len
+    image = np.full(int(record_len.sum()), 10, dtype=np.uint8)
+    image[at] = 62
+    image[_ragged_index(at + 1, name_len)] = names_s.view(np.uint8)[_ragged_index(
+        np.arange(distinct.size, dtype=np.int64) * names_s.dtype.itemsize, name_len)]
+    image[_ragged_index(at + 1 + name_len + 1, seq_len)] = blob[_ragged_index(seq_start, seq_len)]
+    with open(nr_proximal_out, 'wb') as f:
+        f.write(image.tobytes())
+    print('Sparsifying', side, 'table...')
+    prox_order = np.empty(distinct.size, dtype=object)
+    prox_order[rank] = [str(x) for x in np.asarray(names).tolist()]
+    rows = rank[(np.cumsum(own) - 1)[first]]
+    cols = np.repeat(np.arange(len(paths), dtype=np.int64), per_file)
+    print('Building binary matrix...')
+    data = _first_occurrence_coo(rows, cols, distinct.size, len(genome_order))
+    return sparse_utils.LightSparseDataFrame(prox_order.tolist(), genome_order, data)
+
+
+def _consolidate_proximal_with_ctx(ctx, genome_proximals, nr_proximal_out, feature_to_allele, side, output_format, extracted):
+    df = None
+    if output_format != 'sparr':                             # (still NotImplementedError, raised where the host raises it)
+        df = _consolidate_proximal_device(ctx, genome_proximals, nr_proximal_out, feature_to_allele, side, extracted)
+    if df is None:
+        PROXIMAL_PATH_COUNTS['consolidate_host'] += 1
+        return consolidate_proximal(genome_proximals, nr_proximal_out, feature_to_allele, side, output_format=output_format)
+    PROXIMAL_PATH_COUNTS['consolidate_device'] += 1
+    return df
 
 
 # ---------------------------------------------------------------------------
