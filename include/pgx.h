@@ -849,6 +849,42 @@ int pgx_prox_group_dev(pgx_ctx *ctx, const uint8_t *d_blob, const uint64_t *d_of
                        uint32_t flags, int32_t *d_first, int32_t *d_variant, uint32_t *d_n_distinct, void *d_workspace,
                        size_t workspace_bytes, void *stream);
 
+/* Ordered de-duplication of rows of ids and the plurality vote of runs of rows: the device step of extract_annotations
+ * (reference pangenome.py:1702-1810, one OrderedDict.fromkeys per names line and one collections.Counter per gene).
+ * Row r holds the ids tok[row_off[r] .. row_off[r + 1]) (n_rows + 1 offsets, row_off[0] = 0, n_tokens = row_off[n_rows]); ids
+ * are at least 0 and equal ids stand for equal strings. Run u is the rows [run_off[u], run_off[u + 1]) (n_runs + 1 offsets,
+ * run_off[0] = 0, run_off[n_runs] = n_rows, strictly increasing).
+ *   keep[p]    = 1 iff no earlier position of p's row holds the id at p, else 0 (n_tokens bytes)
+ *   L(r)       = the kept ids of row r in order: the empty list for an empty row, and two empty lists are equal
+ *   count(r)   = the rows r' of r's run with L(r') == L(r), element by element
+ *   winner[u]  = the smallest row of run u with the largest count; votes[u] = that count (n_runs entries each)
+ *   differs[r] = 1 iff L(r) != L(winner[run of r]), else 0 (n_rows bytes)
+ * All four are functions of the input alone: the same input gives the same bytes on every call. Hashes only decide where to
+ * look -- two lists are called equal after their lengths and every element have been compared. PGX_ANNOT_NARROW_HASH (a test
+ * seam) keeps only the low 3 bits of every hash: same results, every probe collides. n_rows >= 2^24, n_tokens >= 2^31,
+ * offsets that decrease or do not start at 0, an empty run or runs that do not cover exactly the rows, a negative id (host
+ * entry), unknown flags and too small a workspace fail with PGX_ERR_INVALID before anything is launched or written.
+ * n_rows = 0 (with n_runs = 0) does nothing.
+ *   pgx_annot_vote      HOST pointers; the device buffers stay in the context between calls
+ *   pgx_annot_vote_dev  the caller's DEVICE pointers (row_off 8-byte aligned, tok, run_off, winner and votes 4-byte aligned),
+ *                       n_tokens given by the caller, and workspace (pgx_annot_vote_workspace_bytes(), 16-byte aligned; 0 for
+ *                       sizes that are refused). Plain launches on `stream`, which is synchronised once at the end; inputs are
+ *                       not written, nothing outside the outputs and the workspace is. Offsets and ids are not checked: rows
+ *                       are clamped into [0, n_tokens) and runs into [0, n_rows), so nothing outside the caller's buffers is
+ *                       touched, the result for broken input being unspecified.
+ * pgx_annot_row_tile(): the ids of a row a lane group handles; a longer row goes to the long-row kernel.
+ * pgx_annot_run_tile(): the rows of a run one wave handles; a longer run goes to the workgroup kernel. */
+#define PGX_ANNOT_NARROW_HASH 1u  /* keep only the low 3 bits of every hash: same results, every probe collides */
+uint32_t pgx_annot_row_tile(void);
+uint32_t pgx_annot_run_tile(void);
+size_t pgx_annot_vote_workspace_bytes(uint32_t n_rows, uint64_t n_tokens, uint32_t n_runs);
+int pgx_annot_vote(pgx_ctx *ctx, const int32_t *tok, const uint64_t *row_off, uint32_t n_rows, const uint32_t *run_off,
+                   uint32_t n_runs, uint32_t flags, uint8_t *out_keep, int32_t *out_winner, uint32_t *out_votes,
+                   uint8_t *out_differs);
+int pgx_annot_vote_dev(pgx_ctx *ctx, const int32_t *d_tok, const uint64_t *d_row_off, uint32_t n_rows, uint64_t n_tokens,
+                       const uint32_t *d_run_off, uint32_t n_runs, uint32_t flags, uint8_t *d_keep, int32_t *d_winner,
+                       uint32_t *d_votes, uint8_t *d_differs, void *d_workspace, size_t workspace_bytes, void *stream);
+
 /* feature names (pangenome.py:1944-1969) as fixed-width zero-padded ASCII records (numpy 'S<width>'):
  * <prefix><cluster>[<variant><member>]; variant NULL = gene names */
 int pgx_format_labels(const char *prefix, const char *variant, const int32_t *cluster, const int32_t *member,

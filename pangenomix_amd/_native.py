@@ -72,6 +72,7 @@ BERNOULLI_CD_LOGS = 1                  # PGX_BERNOULLI_CD_LOGS
 ASSOC_BLOCKS, ASSOC_DROP_EMPTY = 1, 2  # PGX_ASSOC_BLOCKS, PGX_ASSOC_DROP_EMPTY
 DICT_NARROW_HASH = 1                   # PGX_DICT_NARROW_HASH
 PROX_NARROW_HASH = 1                   # PGX_PROX_NARROW_HASH
+ANNOT_NARROW_HASH = 1                  # PGX_ANNOT_NARROW_HASH
 ASSOC_NARROW_HASH = 4                  # PGX_ASSOC_NARROW_HASH
 
 
@@ -200,6 +201,12 @@ SIGNATURES = {
     'pgx_prox_cut_dev': (C.c_int, [_P, _P, C.c_uint64, _P, _P, _P, _P, C.c_uint32, _P, _P, _P]),
     'pgx_prox_group': (C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P]),
     'pgx_prox_group_dev': (C.c_int, [_P, _P, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P, _P, C.c_size_t, _P]),
+    'pgx_annot_row_tile': (C.c_uint32, []),
+    'pgx_annot_run_tile': (C.c_uint32, []),
+    'pgx_annot_vote_workspace_bytes': (C.c_size_t, [C.c_uint32, C.c_uint64, C.c_uint32]),
+    'pgx_annot_vote': (C.c_int, [_P, _P, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32, _P, _P, _P, _P]),
+    'pgx_annot_vote_dev': (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint64, _P, C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P,
+                                     C.c_size_t, _P]),
     'pgx_genome_sets_diff': (C.c_int, [_P, _P, _P, C.c_uint64, _P, _P, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P]),
     'pgx_genome_sets_diff_dev': (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P]),
     'pgx_cluster_greedy': (C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(ClusterParams), _P, _P, _P, _P,
@@ -1056,6 +1063,37 @@ class Context(object):
         """The same on device memory (raw device addresses; synchronises `stream`, see pgx.h)."""
         check(lib().pgx_prox_group_dev(self._h, d_blob, d_offsets, d_gene, int(n), int(flags), d_first, d_variant,
                                        d_n_distinct, d_ws, int(ws_bytes), stream))
+
+    # -- rows of ids without repeats, runs of rows voted (pangenome.extract_annotations) -------------------------------------
+    def annot_vote(self, tok, row_off, run_off, flags=0):
+        """(keep uint8 [n_tokens], winner int32 [n_runs], votes uint32 [n_runs], differs uint8 [n_rows]) of the rows
+        tok[row_off[r]:row_off[r + 1]] grouped into the runs [run_off[u], run_off[u + 1]): the first occurrences of a row's
+        ids, the first row of each run's most frequent list of kept ids, how many rows hold that list, and the rows that hold
+        another (pgx.h: pgx_annot_vote). flags: ANNOT_NARROW_HASH, the test seam."""
+        tok = np.ascontiguousarray(tok, dtype=np.int32)
+        row_off = np.ascontiguousarray(row_off, dtype=np.uint64)
+        run_off = np.ascontiguousarray(run_off, dtype=np.uint32)
+        if tok.ndim != 1 or row_off.ndim != 1 or run_off.ndim != 1 or row_off.size < 1 or run_off.size < 1:
+            raise ValueError('tok must be 1-D, row_off hold n_rows + 1 and run_off n_runs + 1 entries')
+        if int(row_off[-1]) > tok.size:
+            raise ValueError('row_off runs past the end of tok')
+        n_rows, n_runs = row_off.size - 1, run_off.size - 1
+        keep = np.zeros(int(row_off[-1]), dtype=np.uint8)
+        winner = np.zeros(n_runs, dtype=np.int32)
+        votes = np.zeros(n_runs, dtype=np.uint32)
+        differs = np.zeros(n_rows, dtype=np.uint8)
+        check(lib().pgx_annot_vote(self._h, _ptr(tok), _ptr(row_off), n_rows, _ptr(run_off), n_runs, int(flags), _ptr(keep),
+                                   _ptr(winner), _ptr(votes), _ptr(differs)))
+        return keep, winner, votes, differs
+
+    def annot_vote_workspace_bytes(self, n_rows, n_tokens, n_runs):
+        return int(lib().pgx_annot_vote_workspace_bytes(int(n_rows), int(n_tokens), int(n_runs)))
+
+    def annot_vote_dev(self, d_tok, d_row_off, n_rows, n_tokens, d_run_off, n_runs, d_keep, d_winner, d_votes, d_differs,
+                       d_ws, ws_bytes, flags=0, stream=0):
+        """The same on device memory (raw device addresses; synchronises `stream`, see pgx.h)."""
+        check(lib().pgx_annot_vote_dev(self._h, d_tok, d_row_off, int(n_rows), int(n_tokens), d_run_off, int(n_runs),
+                                       int(flags), d_keep, d_winner, d_votes, d_differs, d_ws, int(ws_bytes), stream))
 
     def pan_core(self, bits, n_genes, perms):
         perms = np.ascontiguousarray(perms, dtype=np.int32)

@@ -71,6 +71,8 @@ enum DevSlot : int {        // pgx_ctx::arena, through DevBuf
     // prox.hip: pgx_prox_cut (the text, the window arrays in one, output and bad flags in one), then pgx_prox_group (the
     // blob, offsets and genes in one, the workspace, every result in one)
     PX_SLOT_TEXT, PX_SLOT_WINDOWS, PX_SLOT_OUT, PX_SLOT_BLOB, PX_SLOT_RECORDS, PX_SLOT_WS, PX_SLOT_RESULT,
+    // annot.hip: the ids, row and run offsets in one, the workspace, every result in one
+    AN_SLOT_TOK, AN_SLOT_OFFSETS, AN_SLOT_WS, AN_SLOT_RESULT,
     DEV_SLOT_COUNT
 };
 enum HostSlot : int {       // pgx_ctx::host_scratch, through HostVec

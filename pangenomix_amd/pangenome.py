@@ -27,7 +27,9 @@ from __future__ import print_function
 import collections
 import os
 import hashlib
+import shutil
 import subprocess as sp
+import urllib.parse
 
 import numpy as np
 import scipy.sparse
@@ -1023,6 +1025,7 @@ def _parse_gff_regular(data):
     if ls.size and (_PROX_SPACE[arr[ls]].any() or _PROX_SPACE[arr[le - 1]].any()):
         return None                                          # (strip() would change the line: leave it to the host)
     keep = arr[ls] != 35 if ls.size else np.zeros(0, dtype=bool)                     # '#'
+    ls0, le0 = ls, le
     ls, le = ls[keep], le[keep]
     n = ls.size
     tabs = np.flatnonzero(arr == 9)
@@ -1066,14 +1069,27 @@ def _parse_gff_regular(data):
     entry_start = np.where(k == 0, a_start[line], before + 1)[is_eq]
     value_end = np.where(k == count[line] - 1, le[line], after)[is_eq]
     eq, line = sp[is_eq], line[is_eq]
-    is_id = (eq - entry_start == 2) & (at(entry_start) == 73) & (at(entry_start + 1) == 68)
-    eq, value_end, line = eq[is_id], value_end[is_id], line[is_id]
-    last_of_line = np.ones(line.size, dtype=bool)
-    last_of_line[:-1] = line[1:] != line[:-1]                # a later ID entry replaces an earlier one
-    if int(last_of_line.sum()) != n:
+
+    def last_value(key):
+        """(start, end) of the value of the last entry named `key` of every line, (-1, -1) on a line without one"""
+        named = eq - entry_start == len(key)
+        for j, ch in enumerate(key):
+            named &= at(entry_start + j) == ch
+        of_line = line[named]
+        final = np.ones(of_line.size, dtype=bool)
+        final[:-1] = of_line[1:] != of_line[:-1]             # a later entry replaces an earlier one
+        v_start, v_end = np.full(n, -1, dtype=np.int64), np.full(n, -1, dtype=np.int64)
+        v_start[of_line[final]], v_end[of_line[final]] = eq[named][final] + 1, value_end[named][final]
+        return v_start, v_end
+    id_start, id_end = last_value(b'ID')
+    if n and int(id_start.min()) < 0:
         return None                                          # a line without ID
+    # (a comment line of exactly nine fields is a record for extract_annotations, which does not know comments)
+    comments = ~keep
+    comment_records = bool(comments.any() and (np.searchsorted(tabs, le0[comments]) - np.searchsorted(tabs, ls0[comments]) == 8).any())
     return dict(arr=arr, n=n, contig=(c_start, c_end), is_cds=is_cds, start0=start - 1, stop=stop, plus=strand == 43,
-                id=(eq[last_of_line] + 1, value_end[last_of_line]))
+                id=(id_start, id_end), type=(ty, t[:, 2]), product=last_value(b'product'), locus_tag=last_value(b'locus_tag'),
+                comment_records=comment_records)
 
 
 def _parse_fna_regular(data):
@@ -2071,3 +2087,405 @@ def validate_upstream_table(df_upstream, upstream_fna_paths, nr_upstream_fna, al
 def validate_downstream_table(df_downstream, downstream_fna_paths, nr_downstream_fna, allele_names, log_group=1, ctx=None):
     """validate_table_against_fasta for a downstream x genome table (reference :1362-1388)."""
     return validate_table_against_fasta(df_downstream, downstream_fna_paths, nr_downstream_fna, allele_names, log_group, ctx)
+
+
+# ---------------------------------------------------------------------------
+# annotations (reference pangenome.py:1650-1810). Without ctx the two functions are the reference's loops, statement for
+# statement, with urllib.unquote spelt urllib.parse.unquote (the reference raises AttributeError there on Python 3). With a
+# _native.Context, extract_annotations matches protein ids against the GFF keys with the exact dictionary (csrc/dict.hip)
+# and de-duplicates and votes on the device (csrc/annot.hip, DESIGN.md 6l); generate_annotations is one dictionary load and
+# one query. As for the proximal builders, only REGULAR input is handled: for anything else the device function returns
+# None before it has written or printed anything and the host function runs, called exactly as without ctx.
+# ---------------------------------------------------------------------------
+ANNOTATION_PATH_COUNTS = collections.Counter()  # extract_device / extract_host / generate_device / generate_host per call
+_DICT_MAX_KEYS, _DICT_MAX_BYTES, _ANNOT_MAX_TOKENS = 1 << 24, 1 << 32, 1 << 31   # the limits of pgx_dict_* and pgx_annot_vote
+
+
+def _generate_annotations_host(features, annotation_files):
+    import pandas as pd
+    relevant_features = list(features) + []
+    for feature in features:
+        name, cluster_type, cluster_num, variant_type, variant_num = breakdown_feature_name(feature)
+        if variant_type:                                     # variant-level feature
+            relevant_features.append(name + '_' + cluster_type + str(cluster_num))
+    relevant_features = set(relevant_features)
+    relevant_annotations = {}
+    for annot_file in annotation_files:
+        with open(annot_file, 'r') as f:
+            for line in f:
+                data = line.strip().split('\t')
+                feature = data[0]
+                if feature in relevant_features:
+                    relevant_annotations[feature] = ';'.join(data[1:])
+    feature_to_annot = {}
+    for feature in features:
+        if feature in relevant_annotations:                  # direct annotation exists
+            feature_to_annot[feature] = relevant_annotations[feature]
+        else:                                                # possible cluster-level annotation exists
+            name, cluster_type, cluster_num, variant_type, variant_num = breakdown_feature_name(feature)
+            feature_cluster = name + '_' + cluster_type + str(cluster_num)
+            if variant_type is not None and feature_cluster in relevant_annotations:
+                feature_to_annot[feature] = relevant_annotations[feature_cluster]
+            else:                                            # cluster-level annotation is missing
+                feature_to_annot[feature] = np.nan
+    return pd.Series(feature_to_annot, index=features)
+
+
+def _extract_annotations_host(genome_gffs, allele_name_file, annotations_out, batch, collapse_alleles, flexible_locus_tag,
+                              allowed_features):
+    tmp_out = annotations_out + '.tmp'
+    shutil.copyfile(allele_name_file, tmp_out)
+    n_gffs = len(genome_gffs)
+    for g in range(0, n_gffs, batch):
+        annotations = {}
+        for gff in genome_gffs[g:g + batch]:
+            with open(gff, 'r') as f_gff:
+                for line in f_gff:
+                    data = line.strip().split('\t')
+                    if len(data) == 9:
+                        feature_type = data[2]
+                        if allowed_features is None or feature_type in allowed_features:
+                            line_annots = data[-1].split(';')
+                            line_annots = dict(map(lambda x: x.split('='), line_annots))
+                            if 'ID' in line_annots and 'product' in line_annots:
+                                product = urllib.parse.unquote(line_annots['product'])   # replace % hex characters
+                                fid2 = line_annots['ID']
+                                fid3 = None
+                                if 'locus_tag' in line_annots:
+                                    fid3 = fid2 + '|' + line_annots['locus_tag']
+                                if flexible_locus_tag:       # save both names when possible
+                                    annotations[fid2] = product
+                                    if fid3 is not None:
+                                        annotations[fid3] = product
+                                else:                        # save only 3-term, or only 2-term if no locus_tag
+                                    annotations[fid2 if fid3 is None else fid3] = product
+        print('Loaded', len(annotations), 'annotations from batch', g + 1, '-', min(n_gffs, g + batch))
+        with open(tmp_out, 'r') as f_last:
+            with open(tmp_out + '2', 'w+') as f_next:
+                for line in f_last:
+                    data = line.strip().split('\t')
+                    allele, fids = data[0], data[1:]
+                    fids = map(lambda x: annotations[x] if x in annotations else x, fids)
+                    fids = list(collections.OrderedDict.fromkeys(fids))   # remove duplicate annotations
+                    f_next.write(allele + '\t' + '\t'.join(fids) + '\n')
+        shutil.move(tmp_out + '2', tmp_out)                  # remove last round
+    if collapse_alleles:
+        with open(tmp_out, 'r') as f_last:
+            current_cluster = None
+            with open(annotations_out, 'w+') as f_next:
+                for line in f_last:
+                    data = line.strip().split('\t')
+                    allele = data[0]
+                    cluster = __get_gene_from_allele__(allele)
+                    allele_annots = '\t'.join(data[1:])
+                    if current_cluster is None:              # initialize first cluster
+                        current_cluster = cluster
+                        cluster_alleles = [allele]
+                        cluster_annots = [allele_annots]
+                    elif cluster == current_cluster:         # continuing current cluster
+                        cluster_alleles.append(allele)
+                        cluster_annots.append(allele_annots)
+                    else:                                    # start of new cluster: the last one of the file is never written
+                        most_common_annot, count = collections.Counter(cluster_annots).most_common(1)[0]
+                        f_next.write(current_cluster + '\t' + most_common_annot + '\n')
+                        for i, annots in enumerate(cluster_annots):
+                            if annots != most_common_annot:
+                                f_next.write(cluster_alleles[i] + '\t' + annots + '\n')
+                        current_cluster = cluster
+                        cluster_alleles = [allele]
+                        cluster_annots = [allele_annots]
+        os.remove(tmp_out)
+    else:
+        shutil.move(tmp_out, annotations_out)
+
+
+def _spans_blob(arr, starts, ends):
+    """(blob uint8, offsets uint64) of the byte strings arr[starts[i]:ends[i]]"""
+    lens = np.asarray(ends, dtype=np.int64) - np.asarray(starts, dtype=np.int64)
+    offsets = np.zeros(lens.size + 1, dtype=np.uint64)
+    np.cumsum(lens, out=offsets[1:])
+    return arr[_ragged_index(starts, lens)], offsets
+
+
+def _join_blobs(blobs):
+    """several (blob, offsets) end to end"""
+    blob = np.concatenate([b for b, _ in blobs]) if blobs else np.zeros(0, dtype=np.uint8)
+    offsets, base = [np.zeros(1, dtype=np.uint64)], 0
+    for b, off in blobs:
+        offsets.append(off[1:] + np.uint64(base))
+        base += int(off[-1])
+    return blob, np.concatenate(offsets)
+
+
+def _annotation_keys(g, flexible_locus_tag, allowed):
+    """The records of one parsed GFF that extract_annotations stores, in file order: (key blob, key offsets, record of
+    each key, product blob, product offsets), or None if a line is not regular."""
+    if g['comment_records']:
+        return None
+    arr, n = g['arr'], g['n']
+    (p_start, p_end), (l_start, l_end), (i_start, i_end) = g['product'], g['locus_tag'], g['id']
+    take = p_start >= 0
+    if allowed is not None and n:
+        ty_start, ty_end = g['type']
+        take &= np.isin(_fixed_width(arr, ty_start, ty_end - ty_start), allowed) if allowed.size else False
+    rec = np.flatnonzero(take)
+    has_tag = l_start[rec] >= 0
+    # ID|locus_tag is ID, '|' and the tag: three pieces of the file's bytes with a '|' appended to them
+    src = np.concatenate((arr, np.frombuffer(b'|', dtype=np.uint8)))
+    bar = arr.size
+    if flexible_locus_tag:
+        kinds = [(rec, False), (rec[has_tag], True)]
+    else:
+        kinds = [(rec[~has_tag], False), (rec[has_tag], True)]
+    owner = np.concatenate([r for r, _ in kinds])
+    tagged = np.concatenate([np.full(r.size, t, dtype=bool) for r, t in kinds])
+    order = np.argsort(owner, kind='stable')                 # file order; a record's two keys follow each other
+    owner, tagged = owner[order], tagged[order]
+    piece_start = np.stack((i_start[owner], np.full(owner.size, bar, dtype=np.int64), l_start[owner]), axis=1)
+    piece_len = np.stack((i_end[owner] - i_start[owner], tagged.astype(np.int64),
+                          np.where(tagged, l_end[owner] - l_start[owner], 0)), axis=1)
+    piece_start = np.where(piece_len > 0, piece_start, 0)
+    keys = src[_ragged_index(piece_start.reshape(-1), piece_len.reshape(-1))]
+    key_off = np.zeros(owner.size + 1, dtype=np.uint64)
+    np.cumsum(piece_len.sum(axis=1), out=key_off[1:])
+    products, product_off = _spans_blob(arr, p_start[rec], p_end[rec])
+    return keys, key_off, np.searchsorted(rec, owner), products, product_off
+
+
+def _parse_names_regular(data):
+    """The lines of an allele names file as arrays, or None if the file is not regular: arr, n, allele (start, end), gene_end
+    (the last 'A' of the allele, its start for one without), fid (start, end of every protein id, line after line), n_fids."""
+    if not data or not _plain_ascii(data) or data.translate(None, b' \x0b\x0c') != data:
+        return None
+    arr = np.frombuffer(data, dtype=np.uint8)
+    ls, le = _line_spans(arr)
+    if (le <= ls).any():
+        return None                                          # a blank line: the allele '' with one empty id
+    if (arr[ls] == 9).any() or (arr[le - 1] == 9).any():
+        return None                                          # strip() would change the line
+    tabs = np.flatnonzero(arr == 9)
+    if tabs.size > 1 and (np.diff(tabs) == 1).any():
+        return None                                          # an empty id
+    lo = np.searchsorted(tabs, ls)
+    n_fids = np.searchsorted(tabs, le) - lo
+    a_end = np.where(n_fids > 0, tabs[np.minimum(lo, max(tabs.size - 1, 0))] if tabs.size else le, le)
+    f_start = tabs + 1
+    f_end = np.concatenate((tabs[1:], np.zeros(1, dtype=np.int64))) if tabs.size else tabs
+    last_of_line = np.cumsum(n_fids) - 1
+    f_end[last_of_line[n_fids > 0]] = le[n_fids > 0]
+    big_a = np.flatnonzero(arr == 65)
+    of_line = np.searchsorted(ls, big_a, side='right') - 1
+    inside = big_a < a_end[of_line]
+    gene_end = ls.copy()
+    gene_end[of_line[inside]] = big_a[inside]                # ascending positions: the last one of a line stays
+    return dict(arr=arr, n=ls.size, allele=(ls, a_end), gene_end=gene_end, fid=(f_start, f_end), n_fids=n_fids)
+
+
+def _extract_annotations_device(ctx, genome_gffs, allele_name_file, annotations_out, batch, collapse_alleles,
+                                flexible_locus_tag, allowed_features):
+    if isinstance(batch, bool) or not isinstance(batch, int) or batch < 1:
+        return None
+    allowed = None
+    if allowed_features is not None:
+        if not isinstance(allowed_features, (list, tuple, set, frozenset)) or \
+                not all(isinstance(x, str) for x in allowed_features):
+            return None                                      # (`in` on a string is a substring test)
+        allowed = np.array([x.encode('ascii') for x in allowed_features if x.isascii()], dtype='S')
+    genome_gffs = list(genome_gffs)
+    try:
+        with open(allele_name_file, 'rb') as f:
+            names = _parse_names_regular(f.read())
+        if names is None:
+            return None
+        # the GFFs: batches in reverse, file order inside a batch, so that the largest index of a key is the record the
+        # reference keeps -- the last one of the first batch that holds the key
+        n_gffs = len(genome_gffs)
+        batch_starts = list(range(0, n_gffs, batch))
+        parts, batch_of_part = [], []
+        for b in reversed(range(len(batch_starts))):
+            for gff in genome_gffs[batch_starts[b]:batch_starts[b] + batch]:
+                with open(gff, 'rb') as f:
+                    g = _parse_gff_regular(f.read())
+                part = None if g is None else _annotation_keys(g, flexible_locus_tag, allowed)
+                if part is None:
+                    return None
+                parts.append(part)
+                batch_of_part.append(b)
+    except (OSError, TypeError, ValueError):
+        return None
+    keys, key_off = _join_blobs([(p[0], p[1]) for p in parts])
+    products, product_off = _join_blobs([(p[3], p[4]) for p in parts])
+    n_records = np.array([p[4].size - 1 for p in parts], dtype=np.int64)
+    record_base = np.cumsum(n_records) - n_records
+    record_of_key = np.concatenate([p[2] + base for p, base in zip(parts, record_base)]) if parts else np.zeros(0, np.int64)
+    batch_of_key = np.repeat(np.array(batch_of_part, dtype=np.int64), [p[1].size - 1 for p in parts])
+    f_start, f_end = names['fid']
+    fids, fid_off = _spans_blob(names['arr'], f_start, f_end)
+    n_keys, n_products, n_tokens = key_off.size - 1, product_off.size - 1, fid_off.size - 1
+    if max(n_keys, n_products, n_tokens, names['n']) >= _DICT_MAX_KEYS or n_tokens >= _ANNOT_MAX_TOKENS or \
+            max(int(key_off[-1]), int(product_off[-1]), int(fid_off[-1])) >= _DICT_MAX_BYTES:
+        return None
+    # the distinct raw products, decoded once each
+    raw_first = ctx.dict_load(products, product_off)
+    distinct_raw = np.flatnonzero(raw_first == np.arange(n_products))
+    decoded, decoded_id = [], {}
+    text_of_raw = np.zeros(n_products, dtype=np.int64)
+    raw_bytes = products.tobytes()
+    for r in distinct_raw.tolist():
+        text = urllib.parse.unquote(raw_bytes[int(product_off[r]):int(product_off[r + 1])].decode('ascii'))
+        if not text or not text.isascii() or text.strip() != text or '\t' in text or '\n' in text or '\r' in text:
+            return None
+        text_of_raw[r] = decoded_id.setdefault(text, len(decoded))
+        if text_of_raw[r] == len(decoded):
+            decoded.append(text.encode('ascii'))
+    text_of_record = text_of_raw[raw_first]
+    decoded_blob, decoded_off = _blob(decoded)
+    # the keys; a product that is itself a key would be replaced again by a later batch: the host knows how
+    key_first = ctx.dict_load(keys, key_off)
+    if decoded and (ctx.dict_query(decoded_blob, decoded_off) >= 0).any():
+        return None
+    last = ctx.dict_query(fids, fid_off)
+    loaded = np.bincount(np.unique(batch_of_key * _DICT_MAX_KEYS + key_first) // _DICT_MAX_KEYS, minlength=len(batch_starts))
+    # one id space for products and the ids nothing replaced: the first of the equal strings
+    mapped = last >= 0
+    loose = np.flatnonzero(~mapped)
+    loose_blob, loose_off = _spans_blob(names['arr'], f_start[loose], f_end[loose])
+    text_blob, text_off = _join_blobs([(decoded_blob, decoded_off), (loose_blob, loose_off)])
+    if text_off.size - 1 >= _DICT_MAX_KEYS or int(text_off[-1]) >= _DICT_MAX_BYTES:
+        return None
+    text_first = ctx.dict_load(text_blob, text_off)
+    tok = np.zeros(n_tokens, dtype=np.int32)
+    tok[mapped] = text_first[text_of_record[record_of_key[last[mapped]]]]
+    tok[loose] = text_first[len(decoded) + np.arange(loose.size)]
+    n_fids = names['n_fids']
+    row_off = np.zeros(names['n'] + 1, dtype=np.uint64)
+    np.cumsum(n_fids, out=row_off[1:])
+    a_start, a_end = names['allele']
+    if collapse_alleles:
+        genes = _fixed_width(names['arr'], a_start, names['gene_end'] - a_start)
+        run_start = np.flatnonzero(np.concatenate((np.ones(1, dtype=bool), genes[1:] != genes[:-1])))
+    else:
+        run_start = np.arange(names['n'])
+    run_off = np.concatenate((run_start, [names['n']])).astype(np.uint32)
+    keep, winner, votes, differs = ctx.annot_vote(tok, row_off, run_off)
+    # the output, one gather: a line is a name, '\t' + text per kept id ('\t' alone for none), '\n'
+    n_runs = run_off.size - 1
+    if collapse_alleles:
+        # per run but the last: the gene with the winner's list, then the alleles that differ
+        closed = np.arange(names['n']) < int(run_off[n_runs - 1])
+        odd = np.flatnonzero((differs != 0) & closed)
+        heads = np.arange(n_runs - 1)
+        line_run = np.concatenate((heads, np.searchsorted(run_off, odd, side='right') - 1))
+        order = np.argsort(line_run, kind='stable')          # a run's gene line first, its alleles in file order
+        row = np.concatenate((winner[:n_runs - 1].astype(np.int64), odd))[order]
+        name_start = np.concatenate((a_start[run_off[:n_runs - 1].astype(np.int64)], a_start[odd]))[order]
+        name_end = np.concatenate((names['gene_end'][run_off[:n_runs - 1].astype(np.int64)], a_end[odd]))[order]
+    else:
+        row = np.arange(names['n'], dtype=np.int64)
+        name_start, name_end = a_start, a_end
+    kept_pos = np.flatnonzero(keep != 0)
+    kept_off = np.searchsorted(kept_pos, row_off.astype(np.int64))          # kept ids before each row
+    k = kept_off[row + 1] - kept_off[row]
+    line_tok = tok[kept_pos[_ragged_index(kept_off[row], k)]]
+    # the source: the names file, then '\t' + text of every string, then '\t\n'
+    tab = np.frombuffer(b'\t', dtype=np.uint8)
+    text_len = np.diff(text_off.astype(np.int64))
+    tabbed_off = text_off.astype(np.int64) + np.arange(text_off.size)
+    tabbed = np.zeros(int(tabbed_off[-1]), dtype=np.uint8)
+    tabbed[tabbed_off[:-1]] = 9
+    tabbed[_ragged_index(tabbed_off[:-1] + 1, text_len)] = text_blob
+    base_text = names['arr'].size
+    base_end = base_text + tabbed.size
+    src = np.concatenate((names['arr'], tabbed, tab, np.frombuffer(b'\n', dtype=np.uint8)))
+    pieces_off = np.cumsum(k + 2) - (k + 2)
+    n_pieces = int((k + 2).sum())
+    p_start, p_len = np.zeros(n_pieces, dtype=np.int64), np.zeros(n_pieces, dtype=np.int64)
+    is_token = np.ones(n_pieces, dtype=bool)
+    p_start[pieces_off], p_len[pieces_off] = name_start, name_end - name_start
+    ends = pieces_off + k + 1
+    p_start[ends], p_len[ends] = np.where(k > 0, base_end + 1, base_end), np.where(k > 0, 1, 2)
+    is_token[pieces_off] = False
+    is_token[ends] = False
+    p_start[is_token], p_len[is_token] = base_text + tabbed_off[line_tok], text_len[line_tok] + 1
+    out = src[_ragged_index(p_start, p_len)]
+    for b, g in enumerate(batch_starts):
+        print('Loaded', int(loaded[b]), 'annotations from batch', g + 1, '-', min(n_gffs, g + batch))
+    with open(annotations_out, 'wb') as f:
+        f.write(out.tobytes())
+    for stale in (annotations_out + '.tmp', annotations_out + '.tmp2'):
+        if os.path.exists(stale):
+            os.remove(stale)
+    return True
+
+
+def extract_annotations(genome_gffs, allele_name_file, annotations_out, batch=100, collapse_alleles=True,
+                        flexible_locus_tag=False, allowed_features=None, ctx=None):
+    """For an allele names file (usually <name>_allele_names.tsv), replaces every protein id by the product of its GFF
+    record (key ID|locus_tag, or ID without a tag; both with flexible_locus_tag), drops repeats, and with collapse_alleles
+    writes per gene the most common annotation of its alleles followed by the alleles that differ (reference :1702-1810,
+    quirks included: the last gene of the file is never written). ctx: a _native.Context for the device path."""
+    if ctx is not None and _extract_annotations_device(ctx, genome_gffs, allele_name_file, annotations_out, batch,
+                                                       collapse_alleles, flexible_locus_tag, allowed_features):
+        ANNOTATION_PATH_COUNTS['extract_device'] += 1
+        return
+    ANNOTATION_PATH_COUNTS['extract_host'] += 1
+    _extract_annotations_host(genome_gffs, allele_name_file, annotations_out, batch, collapse_alleles, flexible_locus_tag,
+                              allowed_features)
+
+
+def _generate_annotations_device(ctx, features, annotation_files):
+    import pandas as pd
+    index = features
+    try:
+        features = list(features)
+        clusters = []
+        for feature in features:
+            name, cluster_type, cluster_num, variant_type, variant_num = breakdown_feature_name(feature)
+            clusters.append(name + '_' + cluster_type + str(cluster_num) if variant_type else None)
+        if not all(isinstance(x, str) and x.isascii() for x in features):
+            return None
+        datas = []
+        for annot_file in annotation_files:
+            with open(annot_file, 'rb') as f:
+                datas.append(f.read())
+    except Exception:                                        # (the host function raises it again, in its own order)
+        return None
+    data = b''.join(datas)
+    if any(d and not d.endswith(b'\n') for d in datas[:-1]) or not _plain_ascii(data):
+        return None
+    arr = np.frombuffer(data, dtype=np.uint8)
+    ls, le = _line_spans(arr)
+    if ls.size and ((le <= ls).any() or _PROX_SPACE[arr[ls]].any() or _PROX_SPACE[arr[np.maximum(le, 1) - 1]].any()):
+        return None                                          # strip() would change a line
+    tabs = np.flatnonzero(arr == 9)
+    lo = np.searchsorted(tabs, ls)
+    has_tab = np.searchsorted(tabs, le) > lo
+    name_end = np.where(has_tab, tabs[np.minimum(lo, tabs.size - 1)], le) if tabs.size else le
+    keys, key_off = _spans_blob(arr, ls, name_end)
+    queries = features + [c for c in clusters if c is not None]
+    q_blob, q_off = _blob([q.encode('ascii') for q in queries])
+    if max(key_off.size, q_off.size) - 1 >= _DICT_MAX_KEYS or max(int(key_off[-1]), int(q_off[-1])) >= _DICT_MAX_BYTES:
+        return None
+    ctx.dict_load(keys, key_off, want_first=False)           # later line = larger index: last[] is the line that stays
+    last = ctx.dict_query(q_blob, q_off)
+    own = last[:len(features)]
+    of_cluster = np.full(len(features), -1, dtype=np.int64)
+    of_cluster[[i for i, c in enumerate(clusters) if c is not None]] = last[len(features):]
+    line = np.where(own >= 0, own, of_cluster)
+    text = {int(i): ';'.join(data[int(name_end[i]) + 1:int(le[i])].decode('ascii').split('\t')) if has_tab[i] else ''
+            for i in np.unique(line[line >= 0])}
+    feature_to_annot = {feature: (text[int(i)] if i >= 0 else np.nan) for feature, i in zip(features, line.tolist())}
+    return pd.Series(feature_to_annot, index=index)
+
+
+def generate_annotations(features, annotation_files, ctx=None):
+    """A pd.Series of annotations indexed by `features`, from files extract_annotations wrote: a feature's own line, else
+    for a variant the line of its cluster <name>_<type><num>, else np.nan; a later line or file replaces an earlier one
+    (reference :1650-1699). ctx: a _native.Context for the device path."""
+    if ctx is not None:
+        series = _generate_annotations_device(ctx, features, annotation_files)
+        if series is not None:
+            ANNOTATION_PATH_COUNTS['generate_device'] += 1
+            return series
+    ANNOTATION_PATH_COUNTS['generate_host'] += 1
+    return _generate_annotations_host(features, annotation_files)
