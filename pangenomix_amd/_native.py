@@ -849,6 +849,34 @@ class Context(object):
     # -- runs of allele rows (pangenome.validate_gene_table[_dense], extract_dominant_alleles) -----------------------------
     RUNS_OUTPUTS = ('derived', 'diff', 'diff_per_genome', 'diff_per_run', 'total', 'best_allele', 'best_count')
 
+    @staticmethod
+    def _runs_args(run_start, gene_of_run, gene_rows, gene_genomes, want, known, thresholds=()):
+        """What allele_runs and core_select (which alone has thresholds) take alike, coerced and checked in the order both
+        always did: (run_start, n_runs, gene_of_run, gene COO rows, gene COO genomes, thresholds)."""
+        run_start = np.ascontiguousarray(run_start, dtype=np.uint32)
+        if run_start.ndim != 1 or run_start.size < 1:
+            raise ValueError('run_start must hold n_runs + 1 entries')
+        thresholds = np.ascontiguousarray(thresholds, dtype=np.uint32)
+        if thresholds.ndim != 1:
+            raise ValueError('thresholds must be one-dimensional')
+        n_runs = run_start.size - 1
+        g_rows = g_genomes = None
+        if gene_of_run is not None:
+            gene_of_run = np.ascontiguousarray(gene_of_run, dtype=np.int32)
+            if gene_of_run.shape != (n_runs,):
+                raise ValueError('gene_of_run must hold one entry per run')
+            g_rows, g_genomes = _coo_args(gene_rows if gene_rows is not None else [], gene_genomes if gene_genomes is not None else [])
+        unknown = set(want) - set(known)
+        if unknown:
+            raise ValueError('unknown outputs %r' % sorted(unknown))
+        return run_start, n_runs, gene_of_run, g_rows, g_genomes, thresholds
+
+    @staticmethod
+    def _runs_result(out, dup):
+        """(out, (allele duplicates, gene duplicates)); with duplicates nothing was computed and out is None."""
+        dups = (int(dup[0]), int(dup[1]))
+        return (None if any(dups) else out), dups
+
     def allele_runs(self, allele_rows, allele_genomes, n_alleles, n_genomes, run_start, gene_rows=None, gene_genomes=None,
                     n_genes=0, gene_of_run=None, want=RUNS_OUTPUTS):
         """({name: array for name in want}, (allele duplicates, gene duplicates)) of the runs [run_start[r], run_start[r + 1])
@@ -857,19 +885,9 @@ class Context(object):
         'diff_per_run' / 'best_count' uint32, 'total' uint64, 'best_allele' int32. With duplicate coordinates nothing is
         computed and the dict is None."""
         a_rows, a_genomes = _coo_args(allele_rows, allele_genomes)
-        run_start = np.ascontiguousarray(run_start, dtype=np.uint32)
-        if run_start.ndim != 1 or run_start.size < 1:
-            raise ValueError('run_start must hold n_runs + 1 entries')
-        n_runs, n_genomes = run_start.size - 1, int(n_genomes)
-        g_rows = g_genomes = None
-        if gene_of_run is not None:
-            gene_of_run = np.ascontiguousarray(gene_of_run, dtype=np.int32)
-            if gene_of_run.shape != (n_runs,):
-                raise ValueError('gene_of_run must hold one entry per run')
-            g_rows, g_genomes = _coo_args(gene_rows if gene_rows is not None else [], gene_genomes if gene_genomes is not None else [])
-        unknown = set(want) - set(self.RUNS_OUTPUTS)
-        if unknown:
-            raise ValueError('unknown outputs %r' % sorted(unknown))
+        run_start, n_runs, gene_of_run, g_rows, g_genomes, _ = self._runs_args(run_start, gene_of_run, gene_rows, gene_genomes,
+                                                                               want, self.RUNS_OUTPUTS)
+        n_genomes = int(n_genomes)
         stride = lib().pgx_bitmap_stride_words(n_runs)
         shapes = {'derived': ((n_genomes, stride), np.uint64), 'diff': ((n_genomes, stride), np.uint64),
                   'diff_per_genome': (n_genomes, np.uint32), 'diff_per_run': (n_runs, np.uint32), 'total': (n_runs, np.uint64),
@@ -880,8 +898,7 @@ class Context(object):
                                     _ptr(g_genomes), 0 if g_rows is None else g_rows.size, int(n_genes), n_genomes,
                                     _ptr(run_start), n_runs, _ptr(gene_of_run), *[_ptr(out.get(k)) for k in self.RUNS_OUTPUTS],
                                     _ptr(dup)))
-        dups = (int(dup[0]), int(dup[1]))
-        return (None if any(dups) else out), dups
+        return self._runs_result(out, dup)
 
     def allele_runs_dev(self, d_allele_bits, n_alleles, d_gene_bits, n_genes, n_genomes, d_run_start, n_runs, d_gene_of_run,
                         d_derived, d_diff, d_diff_per_genome, d_diff_per_run, d_total, d_best_allele, d_best_count, d_ws,
@@ -902,22 +919,9 @@ class Context(object):
         of n_thresholds int32 arrays, row t cut to n_selected[t]. With duplicate coordinates nothing is computed and the
         dict is None."""
         a_rows, a_genomes = _coo_args(allele_rows, allele_genomes)
-        run_start = np.ascontiguousarray(run_start, dtype=np.uint32)
-        if run_start.ndim != 1 or run_start.size < 1:
-            raise ValueError('run_start must hold n_runs + 1 entries')
-        thresholds = np.ascontiguousarray(thresholds, dtype=np.uint32)
-        if thresholds.ndim != 1:
-            raise ValueError('thresholds must be one-dimensional')
-        n_runs, n_thr = run_start.size - 1, thresholds.size
-        g_rows = g_genomes = None
-        if gene_of_run is not None:
-            gene_of_run = np.ascontiguousarray(gene_of_run, dtype=np.int32)
-            if gene_of_run.shape != (n_runs,):
-                raise ValueError('gene_of_run must hold one entry per run')
-            g_rows, g_genomes = _coo_args(gene_rows if gene_rows is not None else [], gene_genomes if gene_genomes is not None else [])
-        unknown = set(want) - set(self.SELECT_OUTPUTS)
-        if unknown:
-            raise ValueError('unknown outputs %r' % sorted(unknown))
+        run_start, n_runs, gene_of_run, g_rows, g_genomes, thresholds = self._runs_args(
+            run_start, gene_of_run, gene_rows, gene_genomes, want, self.SELECT_OUTPUTS, thresholds)
+        n_thr = thresholds.size
         want = set(want) | ({'n_selected'} if 'selected' in want else set())
         shapes = {'gene_count': (n_runs, np.uint32), 'best_allele': (n_runs, np.int32), 'best_count': (n_runs, np.uint32),
                   'mask': (n_runs, np.uint32), 'selected': ((n_thr, n_runs), np.int32), 'n_selected': (n_thr, np.uint32)}
@@ -927,10 +931,8 @@ class Context(object):
                                     _ptr(g_genomes), 0 if g_rows is None else g_rows.size, int(n_genes), int(n_genomes),
                                     _ptr(run_start), n_runs, _ptr(gene_of_run), _ptr(thresholds), n_thr,
                                     *([_ptr(out.get(k)) for k in self.SELECT_OUTPUTS] + [_ptr(dup)])))
-        dups = (int(dup[0]), int(dup[1]))
-        if any(dups):
-            return None, dups
-        if 'selected' in out:
+        out, dups = self._runs_result(out, dup)
+        if out is not None and 'selected' in out:
             out['selected'] = [out['selected'][t, :int(out['n_selected'][t])].copy() for t in range(n_thr)]
         return out, dups
 

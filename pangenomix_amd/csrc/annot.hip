@@ -499,30 +499,25 @@ int vote_host(pgx_ctx *ctx, const int32_t *tok, const uint64_t *row_off, uint32_
     if (n_rows == 0) return PGX_OK;
     PGX_REQUIRE(out_winner && out_votes && out_differs && (n_tokens == 0 || out_keep), "NULL argument");
     PGX_HIP(hipSetDevice(ctx->device_id));
-    DevBuf d_tok(ctx, AN_SLOT_TOK), d_off(ctx, AN_SLOT_OFFSETS), d_ws(ctx, AN_SLOT_WS), d_out(ctx, AN_SLOT_RESULT);
-    WsLayout lay_off, lay_out;
-    const size_t o_row = lay_off.take(((size_t)n_rows + 1) * 8), o_run = lay_off.take(((size_t)n_runs + 1) * 4);
-    const size_t o_keep = lay_out.take((size_t)n_tokens), o_winner = lay_out.take((size_t)n_runs * 4),
-                 o_votes = lay_out.take((size_t)n_runs * 4), o_differs = lay_out.take(n_rows);
+    DevBuf d_tok(ctx, AN_SLOT_TOK), d_ws(ctx, AN_SLOT_WS);
+    DevPack in(ctx, AN_SLOT_OFFSETS), res(ctx, AN_SLOT_RESULT);
+    const PackPart rows = in.in(row_off, (size_t)n_rows + 1), runs = in.in(run_off, (size_t)n_runs + 1);
+    const PackPart keep = res.out(out_keep, (size_t)n_tokens), winner = res.out(out_winner, n_runs),
+                   votes = res.out(out_votes, n_runs), differs = res.out(out_differs, n_rows);
     PGX_HIP(d_tok.alloc((size_t)n_tokens * 4));
-    PGX_HIP(d_off.alloc(lay_off.off));
-    PGX_HIP(d_out.alloc(lay_out.off));
+    PGX_HIP(in.alloc());
+    PGX_HIP(res.alloc());
     PGX_HIP(d_ws.alloc(vote_layout(n_rows, n_tokens).bytes));
     if (n_tokens) {
         rc = pgx_staged_h2d(ctx, d_tok.p, tok, (size_t)n_tokens * 4, ctx->stream);
         if (rc != PGX_OK) return rc;
     }
-    uint8_t *in = d_off.as<uint8_t>(), *o = d_out.as<uint8_t>();
-    PGX_HIP(hipMemcpyAsync(in + o_row, row_off, ((size_t)n_rows + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-    PGX_HIP(hipMemcpyAsync(in + o_run, run_off, ((size_t)n_runs + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-    rc = vote_launch(ctx, d_tok.as<int32_t>(), (const u64 *)(in + o_row), n_rows, n_tokens, (const uint32_t *)(in + o_run),
-                     n_runs, flags, o + o_keep, (int32_t *)(o + o_winner), (uint32_t *)(o + o_votes), o + o_differs,
+    PGX_HIP(in.upload(ctx->stream));
+    rc = vote_launch(ctx, d_tok.as<int32_t>(), in.dev<u64>(rows), n_rows, n_tokens, in.dev<uint32_t>(runs), n_runs, flags,
+                     res.dev<uint8_t>(keep), res.dev<int32_t>(winner), res.dev<uint32_t>(votes), res.dev<uint8_t>(differs),
                      d_ws.as<uint8_t>(), ctx->stream);
     if (rc != PGX_OK) return rc;
-    if (n_tokens) PGX_HIP(hipMemcpyAsync(out_keep, o + o_keep, (size_t)n_tokens, hipMemcpyDeviceToHost, ctx->stream));
-    PGX_HIP(hipMemcpyAsync(out_winner, o + o_winner, (size_t)n_runs * 4, hipMemcpyDeviceToHost, ctx->stream));
-    PGX_HIP(hipMemcpyAsync(out_votes, o + o_votes, (size_t)n_runs * 4, hipMemcpyDeviceToHost, ctx->stream));
-    PGX_HIP(hipMemcpyAsync(out_differs, o + o_differs, n_rows, hipMemcpyDeviceToHost, ctx->stream));
+    PGX_HIP(res.download(ctx->stream));
     PGX_HIP(hipStreamSynchronize(ctx->stream));
     return PGX_OK;
 }

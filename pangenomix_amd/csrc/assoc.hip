@@ -310,30 +310,26 @@ int assoc_staged(pgx_ctx *ctx, const uint64_t *d_bits, uint32_t src_rows, uint32
     if (n_rows == 0) return PGX_OK;
     hipStream_t stream = ctx->stream;
     const AssocGeom g = make_geom(n_rows, n_sel);
-    DevBuf d_ws(ctx, AS_SLOT_WS), d_rmap(ctx, AS_SLOT_RMAP), d_cmap(ctx, AS_SLOT_CMAP), d_masks(ctx, AS_SLOT_MASKS),
-        d_tp(ctx, AS_SLOT_TP), d_inc(ctx, AS_SLOT_INC), d_block(ctx, AS_SLOT_BLOCK), d_rep(ctx, AS_SLOT_REP);
+    DevBuf d_ws(ctx, AS_SLOT_WS);
+    DevPack in(ctx, AS_SLOT_IN), res(ctx, AS_SLOT_OUT);
+    const PackPart rmap = in.in(row_map, n_rows), cmap = in.in(col_map, n_sel),
+                   target_masks = in.in(masks, (size_t)n_targets * g.words);
+    // block_of_row comes down only with PGX_ASSOC_BLOCKS, rep_row as far as there are blocks (below)
+    const PackPart inc = res.out(out_inc, n_rows), tp = res.out(out_tp, (size_t)n_targets * n_rows),
+                   block = res.out(blocks ? out_block : nullptr, n_rows), rep = res.out<int32_t>(nullptr, n_rows);
     PGX_HIP(d_ws.alloc(g.bytes));
-    PGX_HIP(d_rmap.alloc((size_t)n_rows * 4));
-    PGX_HIP(d_cmap.alloc((size_t)n_sel * 4));
-    PGX_HIP(d_masks.alloc((size_t)n_targets * g.words * 8));
-    PGX_HIP(d_tp.alloc((size_t)n_targets * n_rows * 4));
-    PGX_HIP(d_inc.alloc((size_t)n_rows * 4));
-    PGX_HIP(d_block.alloc((size_t)n_rows * 4));
-    PGX_HIP(d_rep.alloc((size_t)n_rows * 4));
-    if (row_map) PGX_HIP(hipMemcpyAsync(d_rmap.p, row_map, (size_t)n_rows * 4, hipMemcpyHostToDevice, stream));
-    if (col_map && n_sel) PGX_HIP(hipMemcpyAsync(d_cmap.p, col_map, (size_t)n_sel * 4, hipMemcpyHostToDevice, stream));
-    if (n_targets) PGX_HIP(hipMemcpyAsync(d_masks.p, masks, (size_t)n_targets * g.words * 8, hipMemcpyHostToDevice, stream));
+    PGX_HIP(in.alloc());
+    PGX_HIP(res.alloc());
+    PGX_HIP(in.upload(stream));
     uint32_t n_blocks = 0;
-    const int rc = assoc_run(ctx, d_bits, src_rows, n_genomes, row_map ? d_rmap.as<int32_t>() : nullptr, n_rows,
-                             col_map ? d_cmap.as<int32_t>() : nullptr, n_sel, d_masks.as<uint64_t>(), n_targets, flags,
-                             d_tp.as<uint32_t>(), d_inc.as<uint32_t>(), d_block.as<int32_t>(), d_rep.as<int32_t>(), d_ws.p,
-                             g.bytes, stream, &n_blocks);
+    const int rc = assoc_run(ctx, d_bits, src_rows, n_genomes, in.dev_if(row_map, rmap), n_rows,
+                             in.dev_if(col_map, cmap), n_sel, in.dev<uint64_t>(target_masks), n_targets, flags,
+                             res.dev<uint32_t>(tp), res.dev<uint32_t>(inc), res.dev<int32_t>(block), res.dev<int32_t>(rep),
+                             d_ws.p, g.bytes, stream, &n_blocks);
     if (rc != PGX_OK) return rc;
-    PGX_HIP(hipMemcpyAsync(out_inc, d_inc.p, (size_t)n_rows * 4, hipMemcpyDeviceToHost, stream));
-    if (n_targets) PGX_HIP(hipMemcpyAsync(out_tp, d_tp.p, (size_t)n_targets * n_rows * 4, hipMemcpyDeviceToHost, stream));
+    PGX_HIP(res.download(stream));
     if (blocks) {
-        PGX_HIP(hipMemcpyAsync(out_block, d_block.p, (size_t)n_rows * 4, hipMemcpyDeviceToHost, stream));
-        if (n_blocks) PGX_HIP(hipMemcpyAsync(out_rep, d_rep.p, (size_t)n_blocks * 4, hipMemcpyDeviceToHost, stream));
+        PGX_HIP(res.download(rep, 0, n_blocks, out_rep, stream));
         *out_n_blocks = n_blocks;
     }
     PGX_HIP(hipStreamSynchronize(stream));

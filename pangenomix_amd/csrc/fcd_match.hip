@@ -308,27 +308,26 @@ int match_host(pgx_ctx *ctx, uint32_t n_rows, uint32_t n_cols, const int32_t *ro
     PGX_HIP(hipSetDevice(ctx->device_id));
     hipStream_t stream = ctx->stream;
     const MatchGeom g = match_geom(n_rows, n_cols, n2);
-    DevBuf d_lists(ctx, FC_SLOT_M_LISTS), d_ws(ctx, FC_SLOT_M_WS), d_out(ctx, FC_SLOT_M_OUT), d_mat(ctx, FC_SLOT_M_MATRIX);
-    WsLayout lay;
-    size_t at_idx[4], at_off[4];
+    DevBuf d_ws(ctx, FC_SLOT_M_WS);
+    DevPack lists(ctx, FC_SLOT_M_LISTS), res(ctx, FC_SLOT_M_OUT), mat(ctx, FC_SLOT_M_MATRIX);
+    PackPart idx[4], off[4];
     for (int f = 0; f < 4; ++f) {
-        at_idx[f] = lay.take(ne[f] * 4);
-        at_off[f] = lay.take((L[f].n + 1) * 8);
+        idx[f] = lists.in(L[f].idx, ne[f]);
+        off[f] = lists.in(L[f].off, L[f].n + 1);
     }
-    PGX_HIP(d_lists.alloc(lay.off));
+    const PackPart r_match = res.out(out_match, k), r_overlap = res.out(out_overlap, k), r_total = res.out(out_total, 1);
+    PGX_HIP(lists.alloc());
     PGX_HIP(d_ws.alloc(g.bytes));
-    WsLayout out;
-    const size_t at_match = out.take(k * 8), at_overlap = out.take(k * 8), at_total = out.take(8);
-    PGX_HIP(d_out.alloc(out.off));
-    if (out_matrix) PGX_HIP(d_mat.alloc((size_t)n1 * n2 * 8));
-    char *pl = d_lists.as<char>(), *pw = d_ws.as<char>(), *po = d_out.as<char>();
+    PGX_HIP(res.alloc());
+    const PackPart r_matrix = mat.out(out_matrix, out_matrix ? (size_t)n1 * n2 : 0);
+    if (out_matrix) PGX_HIP(mat.alloc());                  // (its slot is not touched otherwise)
+    PGX_HIP(lists.upload(stream));
+    char *pw = d_ws.as<char>();
     const int32_t *d_idx[4];
     const uint64_t *d_off[4];
     for (int f = 0; f < 4; ++f) {
-        d_idx[f] = (const int32_t *)(pl + at_idx[f]);
-        d_off[f] = (const uint64_t *)(pl + at_off[f]);
-        if (ne[f]) PGX_HIP(hipMemcpyAsync(pl + at_idx[f], L[f].idx, ne[f] * 4, hipMemcpyHostToDevice, stream));
-        PGX_HIP(hipMemcpyAsync(pl + at_off[f], L[f].off, (L[f].n + 1) * 8, hipMemcpyHostToDevice, stream));
+        d_idx[f] = lists.dev<int32_t>(idx[f]);
+        d_off[f] = lists.dev<uint64_t>(off[f]);
     }
     unsigned long long *m2r = (unsigned long long *)(pw + g.off_m2r), *m2c = (unsigned long long *)(pw + g.off_m2c);
     unsigned long long *m1r = (unsigned long long *)(pw + g.off_m1r), *m1c = (unsigned long long *)(pw + g.off_m1c);
@@ -336,9 +335,9 @@ int match_host(pgx_ctx *ctx, uint32_t n_rows, uint32_t n_cols, const int32_t *ro
     if (rc != PGX_OK) return rc;
     rc = launch_masks(ctx, d_idx[3], d_off[3], col_off2, 0, (uint32_t)n2, g.stride_c, m2c, stream);
     if (rc != PGX_OK) return rc;
-    rc = match_blocks(ctx, (uint32_t)n1, (uint32_t)n2, g, m2r, m2c, (long long *)(po + at_match),
-                      (unsigned long long *)(po + at_overlap), (unsigned long long *)(po + at_total),
-                      out_matrix ? d_mat.as<unsigned long long>() : nullptr, (unsigned long long *)(pw + g.off_o),
+    rc = match_blocks(ctx, (uint32_t)n1, (uint32_t)n2, g, m2r, m2c, res.dev<long long>(r_match),
+                      res.dev<unsigned long long>(r_overlap), res.dev<unsigned long long>(r_total),
+                      (unsigned long long *)mat.dev_if(out_matrix, r_matrix), (unsigned long long *)(pw + g.off_o),
                       (uint8_t *)(pw + g.off_flags), stream,
                       [&](uint32_t b0, uint32_t nb, const unsigned long long **a, const unsigned long long **b) {
                           int r = launch_masks(ctx, d_idx[0], d_off[0], row_off1, b0, nb, g.stride_r, m1r, stream);
@@ -348,10 +347,8 @@ int match_host(pgx_ctx *ctx, uint32_t n_rows, uint32_t n_cols, const int32_t *ro
                           return r;
                       });
     if (rc != PGX_OK) return rc;
-    PGX_HIP(hipMemcpyAsync(out_match, po + at_match, k * 8, hipMemcpyDeviceToHost, stream));
-    PGX_HIP(hipMemcpyAsync(out_overlap, po + at_overlap, k * 8, hipMemcpyDeviceToHost, stream));
-    PGX_HIP(hipMemcpyAsync(out_total, po + at_total, 8, hipMemcpyDeviceToHost, stream));
-    if (out_matrix) PGX_HIP(hipMemcpyAsync(out_matrix, d_mat.p, (size_t)n1 * n2 * 8, hipMemcpyDeviceToHost, stream));
+    PGX_HIP(res.download(stream));
+    PGX_HIP(mat.download(stream));
     PGX_HIP(hipStreamSynchronize(stream));
     return PGX_OK;
 }

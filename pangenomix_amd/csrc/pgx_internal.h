@@ -7,6 +7,7 @@
 #include <cstring>
 #include "../../include/pgx.h"
 #include "pgx_guard.h"
+#include "pgx_pack.h"
 
 #include <string>
 #include <utility>
@@ -49,16 +50,14 @@ enum DevSlot : int {        // pgx_ctx::arena, through DevBuf
     FC_SLOT_CCOLS, FC_SLOT_CLEARED,
     // fcd_match.hip: the uploaded lists, the workspace, the results, the whole overlap matrix when it is asked for
     FC_SLOT_M_LISTS, FC_SLOT_M_WS, FC_SLOT_M_OUT, FC_SLOT_M_MATRIX,
-    // assoc.hip
-    AS_SLOT_BITS, AS_SLOT_ROWS, AS_SLOT_GENOMES, AS_SLOT_CNT, AS_SLOT_WS, AS_SLOT_RMAP, AS_SLOT_CMAP, AS_SLOT_MASKS,
-    AS_SLOT_TP, AS_SLOT_INC, AS_SLOT_BLOCK, AS_SLOT_REP,
-    // runs.hip
+    // assoc.hip: the table, the workspace, the maps and masks in one, every result in one
+    AS_SLOT_BITS, AS_SLOT_ROWS, AS_SLOT_GENOMES, AS_SLOT_CNT, AS_SLOT_WS, AS_SLOT_IN, AS_SLOT_OUT,
+    // runs.hip: the allele table and the gene table, run_start and gene_of_run in one (pgx_runs_load_host fills these for
+    // select.hip too), then its own workspace and every result in one
     RN_SLOT_ABITS, RN_SLOT_AROWS, RN_SLOT_AGENOMES, RN_SLOT_ACNT, RN_SLOT_GBITS, RN_SLOT_GROWS, RN_SLOT_GGENOMES,
-    RN_SLOT_GCNT, RN_SLOT_WS, RN_SLOT_START, RN_SLOT_GENE, RN_SLOT_DERIVED, RN_SLOT_DIFF, RN_SLOT_PER_GENOME,
-    RN_SLOT_PER_RUN, RN_SLOT_TOTAL, RN_SLOT_BEST, RN_SLOT_BEST_COUNT,
-    // select.hip: the two tables as runs.hip keeps them, the workspace, the run arrays, the thresholds, every result in one
-    CS_SLOT_ABITS, CS_SLOT_AROWS, CS_SLOT_AGENOMES, CS_SLOT_ACNT, CS_SLOT_GBITS, CS_SLOT_GROWS, CS_SLOT_GGENOMES,
-    CS_SLOT_GCNT, CS_SLOT_WS, CS_SLOT_START, CS_SLOT_GENE, CS_SLOT_THR, CS_SLOT_OUT,
+    RN_SLOT_GCNT, RN_SLOT_IN, RN_SLOT_WS, RN_SLOT_OUT,
+    // select.hip: the workspace, the thresholds, every result in one
+    CS_SLOT_WS, CS_SLOT_THR, CS_SLOT_OUT,
     // scan.hip
     SC_SLOT_TEXT, SC_SLOT_KEYS, SC_SLOT_FOUND, SC_SLOT_WS,
     // bernoulli_cd.hip
@@ -269,13 +268,48 @@ struct DevBuf {
     }
 };
 
-// Layout of a workspace in one allocation: every part starts at a multiple of 256 bytes.
-struct WsLayout {
-    size_t off = 0;
-    size_t take(size_t bytes) {
-        const size_t o = off;
-        off += (bytes + 255) & ~(size_t)255;
-        return o;
+// Layout of a workspace in one allocation, by offsets alone: take() is where the part starts, `off` the size so far.
+struct WsLayout : PackLayout {
+    size_t take(size_t bytes) { return add(bytes).off; }
+};
+
+// Host arrays <-> the parts of ONE slot, for the host entries: an array's size is stated once, where in() / out() registers
+// it; the allocation and both copies follow from that. Register every part, alloc(), upload() before the launches, download()
+// after them: one hipMemcpyAsync per array in registration order, straight from / to the caller's memory, and nothing here
+// synchronises. A NULL host pointer reserves a part that is never copied; neither is a part of 0 bytes.
+struct DevPack {
+    DevBuf buf;
+    PackLayout lay;
+    struct Bound { PackPart part; void *host; bool up; };
+    std::vector<Bound> bound;
+    DevPack(pgx_ctx *c, DevSlot s) : buf(c, s) {}
+    template <typename T> PackPart in(const T *host, size_t count) { return bind(const_cast<T *>(host), count * sizeof(T), true); }
+    template <typename T> PackPart out(T *host, size_t count) { return bind(host, count * sizeof(T), false); }
+    hipError_t alloc() { return buf.alloc(lay.total()); }
+    template <typename T> T *dev(const PackPart &part) { return reinterpret_cast<T *>(static_cast<char *>(buf.p) + part.off); }
+    template <typename T> T *dev_if(const T *host, const PackPart &part) { return host ? dev<T>(part) : nullptr; }  // NULL: not wanted
+    hipError_t upload(hipStream_t stream) { return copy(true, stream); }
+    hipError_t download(hipStream_t stream) { return copy(false, stream); }
+    // elements [first, first + count) of a part to `host`: an array of which only the device knew how much it would write
+    template <typename T> hipError_t download(const PackPart &part, size_t first, size_t count, T *host, hipStream_t stream) {
+        if ((first + count) * sizeof(T) > part.bytes) return hipErrorInvalidValue;
+        return count ? hipMemcpyAsync(host, dev<T>(part) + first, count * sizeof(T), hipMemcpyDeviceToHost, stream) : hipSuccess;
+    }
+
+private:
+    PackPart bind(void *host, size_t bytes, bool up) {
+        const PackPart part = lay.add(bytes);
+        if (host && bytes) bound.push_back({part, host, up});
+        return part;
+    }
+    hipError_t copy(bool up, hipStream_t stream) {
+        for (const Bound &b : bound) {
+            void *d = dev<char>(b.part);
+            const hipError_t e = b.up != up ? hipSuccess : hipMemcpyAsync(up ? d : b.host, up ? b.host : d, b.part.bytes,
+                                                                          up ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost, stream);
+            if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
     }
 };
 
@@ -329,6 +363,19 @@ int pgx_rccl_all_gather_u64(pgx_ctx *ctx, const void *send, void *recv, size_t c
 const char *pgx_runs_host_error(const uint32_t *run_start, uint32_t n_runs, const int32_t *gene_of_run, uint32_t n_alleles,
                                 uint32_t n_genes);
 const char *pgx_runs_status_error(uint32_t status);
+// The host entries' common start: the record and run arrays checked (messages under the name `who`), both tables built (the
+// gene table only with gene_of_run), their counters read back -- ctx->stream is synchronised -- and reported through
+// out_duplicates (2 x u64 unless NULL), run_start / gene_of_run enqueued. `nothing`: duplicates or no runs, the caller returns.
+struct RunsLoaded {
+    const uint64_t *d_abits, *d_gbits;          // d_gbits and d_gene_of_run: NULL without gene_of_run
+    const uint32_t *d_run_start;
+    const int32_t *d_gene_of_run;
+    bool nothing;
+};
+int pgx_runs_load_host(pgx_ctx *ctx, const char *who, const int32_t *a_rows, const int32_t *a_genomes, uint64_t a_records,
+                       uint32_t n_alleles, const int32_t *g_rows, const int32_t *g_genomes, uint64_t g_records, uint32_t n_genes,
+                       uint32_t n_genomes, const uint32_t *run_start, uint32_t n_runs, const int32_t *gene_of_run,
+                       uint64_t *out_duplicates, RunsLoaded *out);
 int pgx_runs_check_enqueue(pgx_ctx *ctx, const uint32_t *d_run_start, const int32_t *d_gene_of_run, uint32_t n_runs,
                            uint32_t n_alleles, uint32_t n_genes, uint32_t *d_status, hipStream_t stream);
 int pgx_runs_stats_enqueue(pgx_ctx *ctx, const uint64_t *d_abits, uint32_t n_alleles, uint32_t n_genomes,

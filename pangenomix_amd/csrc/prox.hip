@@ -449,30 +449,24 @@ int cut_host(pgx_ctx *ctx, const uint8_t *text, u64 text_bytes, const uint64_t *
     PGX_REQUIRE(total < (1ull << 32), "the output must hold fewer than 2^32 bytes");
     PGX_REQUIRE(total == 0 || out, "NULL out");
     PGX_HIP(hipSetDevice(ctx->device_id));
-    DevBuf d_text(ctx, PX_SLOT_TEXT), d_win(ctx, PX_SLOT_WINDOWS), d_out(ctx, PX_SLOT_OUT);
+    DevBuf d_text(ctx, PX_SLOT_TEXT);
+    DevPack win(ctx, PX_SLOT_WINDOWS), res(ctx, PX_SLOT_OUT);
+    const PackPart w_start = win.in(start, n), w_off = win.in(off.data(), (size_t)n + 1), w_len = win.in(length, n),
+                   w_rev = win.in(reverse, n);
+    const PackPart r_out = res.out(out, (size_t)total), r_bad = res.out(out_bad, n);
     PGX_HIP(d_text.alloc((size_t)text_bytes));
-    // the windows in one buffer: start, out_offsets (8 bytes each), length (4), reverse (1), then bad behind the output
-    WsLayout lay;
-    const size_t o_start = lay.take((size_t)n * 8), o_off = lay.take(((size_t)n + 1) * 8), o_len = lay.take((size_t)n * 4),
-                 o_rev = lay.take(n);
-    PGX_HIP(d_win.alloc(lay.off));
-    WsLayout lay_out;
-    const size_t o_out = lay_out.take((size_t)total), o_bad = lay_out.take(n);
-    PGX_HIP(d_out.alloc(lay_out.off));
-    uint8_t *w = d_win.as<uint8_t>(), *o = d_out.as<uint8_t>();
+    PGX_HIP(win.alloc());
+    PGX_HIP(res.alloc());
     if (text_bytes) {
         int rc = pgx_staged_h2d(ctx, d_text.p, text, (size_t)text_bytes, ctx->stream);
         if (rc != PGX_OK) return rc;
     }
-    PGX_HIP(hipMemcpyAsync(w + o_start, start, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-    PGX_HIP(hipMemcpyAsync(w + o_off, off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-    PGX_HIP(hipMemcpyAsync(w + o_len, length, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-    PGX_HIP(hipMemcpyAsync(w + o_rev, reverse, n, hipMemcpyHostToDevice, ctx->stream));
-    int rc = cut_launch(ctx, d_text.as<uint8_t>(), text_bytes, (const u64 *)(w + o_start), (const uint32_t *)(w + o_len),
-                        w + o_rev, (const u64 *)(w + o_off), n, o + o_out, o + o_bad, ctx->stream);
+    PGX_HIP(win.upload(ctx->stream));
+    int rc = cut_launch(ctx, d_text.as<uint8_t>(), text_bytes, win.dev<u64>(w_start), win.dev<uint32_t>(w_len),
+                        win.dev<uint8_t>(w_rev), win.dev<u64>(w_off), n, res.dev<uint8_t>(r_out), res.dev<uint8_t>(r_bad),
+                        ctx->stream);
     if (rc != PGX_OK) return rc;
-    if (total) PGX_HIP(hipMemcpyAsync(out, o + o_out, (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
-    PGX_HIP(hipMemcpyAsync(out_bad, o + o_bad, n, hipMemcpyDeviceToHost, ctx->stream));
+    PGX_HIP(res.download(ctx->stream));
     PGX_HIP(hipStreamSynchronize(ctx->stream));
     return PGX_OK;
 }
@@ -613,29 +607,24 @@ int group_host(pgx_ctx *ctx, const uint8_t *blob, const uint64_t *offsets, const
     }
     PGX_REQUIRE(out_first && out_variant, "NULL argument");
     PGX_HIP(hipSetDevice(ctx->device_id));
-    DevBuf d_blob(ctx, PX_SLOT_BLOB), d_in(ctx, PX_SLOT_RECORDS), d_ws(ctx, PX_SLOT_WS), d_out(ctx, PX_SLOT_RESULT);
+    DevBuf d_blob(ctx, PX_SLOT_BLOB), d_ws(ctx, PX_SLOT_WS);
+    DevPack in(ctx, PX_SLOT_RECORDS), res(ctx, PX_SLOT_RESULT);
     const size_t bytes = (size_t)offsets[n];
+    const PackPart i_off = in.in(offsets, (size_t)n + 1), i_gene = in.in(gene, n);
+    const PackPart r_first = res.out(out_first, n), r_variant = res.out(out_variant, n), r_distinct = res.out(out_distinct, 1);
     PGX_HIP(d_blob.alloc(bytes));
-    WsLayout lay_in, lay_out;
-    const size_t o_off = lay_in.take(((size_t)n + 1) * 8), o_gene = lay_in.take((size_t)n * 4);
-    const size_t o_first = lay_out.take((size_t)n * 4), o_variant = lay_out.take((size_t)n * 4), o_distinct = lay_out.take(4);
-    PGX_HIP(d_in.alloc(lay_in.off));
-    PGX_HIP(d_out.alloc(lay_out.off));
+    PGX_HIP(in.alloc());
+    PGX_HIP(res.alloc());
     PGX_HIP(d_ws.alloc(group_layout(n).bytes));
     if (bytes) {
         rc = pgx_staged_h2d(ctx, d_blob.p, blob, bytes, ctx->stream);
         if (rc != PGX_OK) return rc;
     }
-    uint8_t *in = d_in.as<uint8_t>(), *o = d_out.as<uint8_t>();
-    PGX_HIP(hipMemcpyAsync(in + o_off, offsets, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-    PGX_HIP(hipMemcpyAsync(in + o_gene, gene, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-    rc = group_launch(ctx, d_blob.as<uint8_t>(), (const u64 *)(in + o_off), (const int32_t *)(in + o_gene), n, flags,
-                      (int32_t *)(o + o_first), (int32_t *)(o + o_variant), (uint32_t *)(o + o_distinct), d_ws.as<uint8_t>(),
-                      ctx->stream);
+    PGX_HIP(in.upload(ctx->stream));
+    rc = group_launch(ctx, d_blob.as<uint8_t>(), in.dev<u64>(i_off), in.dev<int32_t>(i_gene), n, flags, res.dev<int32_t>(r_first),
+                      res.dev<int32_t>(r_variant), res.dev<uint32_t>(r_distinct), d_ws.as<uint8_t>(), ctx->stream);
     if (rc != PGX_OK) return rc;
-    PGX_HIP(hipMemcpyAsync(out_first, o + o_first, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    PGX_HIP(hipMemcpyAsync(out_variant, o + o_variant, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    PGX_HIP(hipMemcpyAsync(out_distinct, o + o_distinct, 4, hipMemcpyDeviceToHost, ctx->stream));
+    PGX_HIP(res.download(ctx->stream));
     PGX_HIP(hipStreamSynchronize(ctx->stream));
     return PGX_OK;
 }

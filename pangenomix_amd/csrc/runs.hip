@@ -195,6 +195,41 @@ int pgx_runs_stats_enqueue(pgx_ctx *ctx, const uint64_t *d_abits, uint32_t n_all
     return PGX_OK;
 }
 
+int pgx_runs_load_host(pgx_ctx *ctx, const char *who, const int32_t *a_rows, const int32_t *a_genomes, uint64_t a_records,
+                       uint32_t n_alleles, const int32_t *g_rows, const int32_t *g_genomes, uint64_t g_records, uint32_t n_genes,
+                       uint32_t n_genomes, const uint32_t *run_start, uint32_t n_runs, const int32_t *gene_of_run,
+                       uint64_t *out_duplicates, RunsLoaded *out) {
+    // the run arrays are host memory here: refused before anything is uploaded or launched
+    const bool records = (a_records == 0 || (a_rows && a_genomes)) && (!gene_of_run || g_records == 0 || (g_rows && g_genomes));
+    const char *broken = records ? pgx_runs_host_error(run_start, n_runs, gene_of_run, n_alleles, n_genes) : "NULL record arrays";
+    if (broken) {
+        pgx_set_error("%s: %s", who, broken);
+        return PGX_ERR_INVALID;
+    }
+    if (out_duplicates) out_duplicates[0] = out_duplicates[1] = 0;
+    PGX_HIP(hipSetDevice(ctx->device_id));
+    DevBuf d_abits(ctx, RN_SLOT_ABITS), d_acnt(ctx, RN_SLOT_ACNT), d_gbits(ctx, RN_SLOT_GBITS), d_gcnt(ctx, RN_SLOT_GCNT);
+    uint64_t dup[2] = {0, 0};
+    int rc = pgx_upload_and_build_bitmap(ctx, a_rows, a_genomes, a_records, n_alleles, n_genomes, RN_SLOT_AROWS,
+                                         RN_SLOT_AGENOMES, d_abits, d_acnt);
+    if (rc == PGX_OK && gene_of_run)
+        rc = pgx_upload_and_build_bitmap(ctx, g_rows, g_genomes, g_records, n_genes, n_genomes, RN_SLOT_GROWS, RN_SLOT_GGENOMES,
+                                         d_gbits, d_gcnt);
+    if (rc == PGX_OK) rc = pgx_read_record_counters(ctx, d_acnt, &dup[0]);
+    if (rc == PGX_OK && gene_of_run) rc = pgx_read_record_counters(ctx, d_gcnt, &dup[1]);
+    if (rc != PGX_OK) return rc;
+    if (out_duplicates) { out_duplicates[0] = dup[0]; out_duplicates[1] = dup[1]; }
+    *out = {nullptr, nullptr, nullptr, nullptr, dup[0] || dup[1] || n_runs == 0};   // not 0/1 tables: nothing is computed
+    if (out->nothing) return PGX_OK;
+    DevPack arrays(ctx, RN_SLOT_IN);
+    const PackPart start = arrays.in(run_start, (size_t)n_runs + 1), gene = arrays.in(gene_of_run, n_runs);
+    PGX_HIP(arrays.alloc());
+    PGX_HIP(arrays.upload(ctx->stream));
+    *out = {d_abits.as<uint64_t>(), gene_of_run ? d_gbits.as<uint64_t>() : nullptr, arrays.dev<uint32_t>(start),
+            arrays.dev_if(gene_of_run, gene), false};
+    return PGX_OK;
+}
+
 namespace {
 
 struct RunsOut {
@@ -277,66 +312,29 @@ int runs_host(pgx_ctx *ctx, const int32_t *a_rows, const int32_t *a_genomes, uin
               uint64_t *out_duplicates) {
     int rc = runs_args(ctx, n_alleles, n_runs, n_genomes, n_genes, run_start, out);
     if (rc != PGX_OK) return rc;
-    PGX_REQUIRE(a_records == 0 || (a_rows && a_genomes), "NULL record arrays");
-    PGX_REQUIRE(!gene_of_run || g_records == 0 || (g_rows && g_genomes), "NULL record arrays");
-    // the run arrays are host memory here: refused before anything is uploaded or launched
-    const char *broken = pgx_runs_host_error(run_start, n_runs, gene_of_run, n_alleles, n_genes);
-    PGX_REQUIRE(!broken, broken);
-    if (out_duplicates) out_duplicates[0] = out_duplicates[1] = 0;
-    PGX_HIP(hipSetDevice(ctx->device_id));
-    hipStream_t stream = ctx->stream;
-    DevBuf d_abits(ctx, RN_SLOT_ABITS), d_acnt(ctx, RN_SLOT_ACNT), d_gbits(ctx, RN_SLOT_GBITS), d_gcnt(ctx, RN_SLOT_GCNT);
-    uint64_t dup[2] = {0, 0};
-    rc = pgx_upload_and_build_bitmap(ctx, a_rows, a_genomes, a_records, n_alleles, n_genomes, RN_SLOT_AROWS, RN_SLOT_AGENOMES,
-                                     d_abits, d_acnt);
-    if (rc == PGX_OK && gene_of_run)
-        rc = pgx_upload_and_build_bitmap(ctx, g_rows, g_genomes, g_records, n_genes, n_genomes, RN_SLOT_GROWS, RN_SLOT_GGENOMES,
-                                         d_gbits, d_gcnt);
-    if (rc == PGX_OK) rc = pgx_read_record_counters(ctx, d_acnt, &dup[0]);
-    if (rc == PGX_OK && gene_of_run) rc = pgx_read_record_counters(ctx, d_gcnt, &dup[1]);
-    if (rc != PGX_OK) return rc;
-    if (out_duplicates) { out_duplicates[0] = dup[0]; out_duplicates[1] = dup[1]; }
-    if (dup[0] || dup[1] || n_runs == 0) return PGX_OK;       // not 0/1 tables: nothing is computed
-
+    RunsLoaded in;
+    rc = pgx_runs_load_host(ctx, __func__, a_rows, a_genomes, a_records, n_alleles, g_rows, g_genomes, g_records, n_genes,
+                            n_genomes, run_start, n_runs, gene_of_run, out_duplicates, &in);
+    if (rc != PGX_OK || in.nothing) return rc;
     const RunsGeom g = make_geom(n_alleles, n_runs, n_genomes);
-    const size_t out_bytes = (size_t)n_genomes * g.o_stride * 8;
-    DevBuf d_ws(ctx, RN_SLOT_WS), d_start(ctx, RN_SLOT_START), d_gene(ctx, RN_SLOT_GENE), d_derived(ctx, RN_SLOT_DERIVED),
-        d_diff(ctx, RN_SLOT_DIFF), d_per_genome(ctx, RN_SLOT_PER_GENOME), d_per_run(ctx, RN_SLOT_PER_RUN),
-        d_total(ctx, RN_SLOT_TOTAL), d_best(ctx, RN_SLOT_BEST), d_best_count(ctx, RN_SLOT_BEST_COUNT);
+    const size_t bitmap_words = (size_t)n_genomes * g.o_stride;
+    DevBuf d_ws(ctx, RN_SLOT_WS);
+    DevPack res(ctx, RN_SLOT_OUT);                            // a bitmap that was not asked for takes no room
+    const PackPart derived = res.out(out.derived, out.derived ? bitmap_words : 0),
+                   diff = res.out(out.diff, out.diff ? bitmap_words : 0),
+                   per_genome = res.out(out.diff_per_genome, n_genomes), per_run = res.out(out.diff_per_run, n_runs),
+                   total = res.out(out.total, n_runs), best = res.out(out.best_allele, n_runs),
+                   best_count = res.out(out.best_count, n_runs);
     PGX_HIP(d_ws.alloc(g.bytes));
-    PGX_HIP(d_start.alloc(((size_t)n_runs + 1) * 4));
-    PGX_HIP(d_gene.alloc((size_t)n_runs * 4));
-    PGX_HIP(d_derived.alloc(out.derived ? out_bytes : 0));
-    PGX_HIP(d_diff.alloc(out.diff ? out_bytes : 0));
-    PGX_HIP(d_per_genome.alloc((size_t)n_genomes * 4));
-    PGX_HIP(d_per_run.alloc((size_t)n_runs * 4));
-    PGX_HIP(d_total.alloc((size_t)n_runs * 8));
-    PGX_HIP(d_best.alloc((size_t)n_runs * 4));
-    PGX_HIP(d_best_count.alloc((size_t)n_runs * 4));
-    PGX_HIP(hipMemcpyAsync(d_start.p, run_start, ((size_t)n_runs + 1) * 4, hipMemcpyHostToDevice, stream));
-    if (gene_of_run) PGX_HIP(hipMemcpyAsync(d_gene.p, gene_of_run, (size_t)n_runs * 4, hipMemcpyHostToDevice, stream));
-    RunsOut dev;
-    dev.derived = out.derived ? d_derived.as<uint64_t>() : nullptr;
-    dev.diff = out.diff ? d_diff.as<uint64_t>() : nullptr;
-    dev.diff_per_genome = out.diff_per_genome ? d_per_genome.as<uint32_t>() : nullptr;
-    dev.diff_per_run = out.diff_per_run ? d_per_run.as<uint32_t>() : nullptr;
-    dev.total = out.total ? d_total.as<uint64_t>() : nullptr;
-    dev.best_allele = out.best_allele ? d_best.as<int32_t>() : nullptr;
-    dev.best_count = out.best_count ? d_best_count.as<uint32_t>() : nullptr;
-    rc = runs_run(ctx, d_abits.as<uint64_t>(), n_alleles, gene_of_run ? d_gbits.as<uint64_t>() : nullptr, n_genes, n_genomes,
-                  d_start.as<uint32_t>(), n_runs, gene_of_run ? d_gene.as<int32_t>() : nullptr, dev, d_ws.p, g.bytes, stream);
+    PGX_HIP(res.alloc());
+    const RunsOut dev = {res.dev_if(out.derived, derived), res.dev_if(out.diff, diff), res.dev_if(out.diff_per_genome, per_genome),
+                         res.dev_if(out.diff_per_run, per_run), res.dev_if(out.total, total), res.dev_if(out.best_allele, best),
+                         res.dev_if(out.best_count, best_count)};
+    rc = runs_run(ctx, in.d_abits, n_alleles, in.d_gbits, n_genes, n_genomes, in.d_run_start, n_runs, in.d_gene_of_run, dev,
+                  d_ws.p, g.bytes, ctx->stream);
     if (rc != PGX_OK) return rc;
-    auto down = [&](void *dst, const void *src, size_t bytes) {
-        return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream) : hipSuccess;
-    };
-    PGX_HIP(down(out.derived, d_derived.p, out_bytes));
-    PGX_HIP(down(out.diff, d_diff.p, out_bytes));
-    PGX_HIP(down(out.diff_per_genome, d_per_genome.p, (size_t)n_genomes * 4));
-    PGX_HIP(down(out.diff_per_run, d_per_run.p, (size_t)n_runs * 4));
-    PGX_HIP(down(out.total, d_total.p, (size_t)n_runs * 8));
-    PGX_HIP(down(out.best_allele, d_best.p, (size_t)n_runs * 4));
-    PGX_HIP(down(out.best_count, d_best_count.p, (size_t)n_runs * 4));
-    PGX_HIP(hipStreamSynchronize(stream));
+    PGX_HIP(res.download(ctx->stream));
+    PGX_HIP(hipStreamSynchronize(ctx->stream));
     return PGX_OK;
 }
 

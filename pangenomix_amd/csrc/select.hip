@@ -245,71 +245,38 @@ int select_host(pgx_ctx *ctx, const int32_t *a_rows, const int32_t *a_genomes, u
                 uint32_t n_thresholds, const SelectOut &out, uint64_t *out_duplicates) {
     int rc = select_args(ctx, n_alleles, n_runs, n_genomes, n_genes, run_start, thresholds, n_thresholds, out);
     if (rc != PGX_OK) return rc;
-    PGX_REQUIRE(a_records == 0 || (a_rows && a_genomes), "NULL record arrays");
-    PGX_REQUIRE(!gene_of_run || g_records == 0 || (g_rows && g_genomes), "NULL record arrays");
-    // the run arrays are host memory here: refused before anything is uploaded or launched
-    const char *broken = pgx_runs_host_error(run_start, n_runs, gene_of_run, n_alleles, n_genes);
-    PGX_REQUIRE(!broken, broken);
-    if (out_duplicates) out_duplicates[0] = out_duplicates[1] = 0;
-    PGX_HIP(hipSetDevice(ctx->device_id));
-    hipStream_t stream = ctx->stream;
-    DevBuf d_abits(ctx, CS_SLOT_ABITS), d_acnt(ctx, CS_SLOT_ACNT), d_gbits(ctx, CS_SLOT_GBITS), d_gcnt(ctx, CS_SLOT_GCNT);
-    uint64_t dup[2] = {0, 0};
-    rc = pgx_upload_and_build_bitmap(ctx, a_rows, a_genomes, a_records, n_alleles, n_genomes, CS_SLOT_AROWS, CS_SLOT_AGENOMES,
-                                     d_abits, d_acnt);
-    if (rc == PGX_OK && gene_of_run)
-        rc = pgx_upload_and_build_bitmap(ctx, g_rows, g_genomes, g_records, n_genes, n_genomes, CS_SLOT_GROWS, CS_SLOT_GGENOMES,
-                                         d_gbits, d_gcnt);
-    if (rc == PGX_OK) rc = pgx_read_record_counters(ctx, d_acnt, &dup[0]);
-    if (rc == PGX_OK && gene_of_run) rc = pgx_read_record_counters(ctx, d_gcnt, &dup[1]);
-    if (rc != PGX_OK) return rc;
-    if (out_duplicates) { out_duplicates[0] = dup[0]; out_duplicates[1] = dup[1]; }
-    if (dup[0] || dup[1] || n_runs == 0) return PGX_OK;       // not 0/1 tables: nothing is computed
-
+    RunsLoaded in;
+    rc = pgx_runs_load_host(ctx, __func__, a_rows, a_genomes, a_records, n_alleles, g_rows, g_genomes, g_records, n_genes,
+                            n_genomes, run_start, n_runs, gene_of_run, out_duplicates, &in);
+    if (rc != PGX_OK || in.nothing) return rc;
     const SelectGeom g = make_geom(n_alleles, n_genes, n_runs);
-    WsLayout lay;                                             // every result in one buffer
-    const size_t per_run = (size_t)n_runs * 4;
-    const size_t off_gene = lay.take(per_run), off_best = lay.take(per_run), off_bcount = lay.take(per_run),
-                 off_mask = lay.take(per_run), off_nsel = lay.take(CS_MAX_THRESHOLDS * 4),
-                 off_sel = lay.take(out.selected ? per_run * n_thresholds : 0);
-    DevBuf d_ws(ctx, CS_SLOT_WS), d_start(ctx, CS_SLOT_START), d_gene(ctx, CS_SLOT_GENE), d_thr(ctx, CS_SLOT_THR),
-        d_out(ctx, CS_SLOT_OUT);
+    DevBuf d_ws(ctx, CS_SLOT_WS);
+    DevPack thr(ctx, CS_SLOT_THR), res(ctx, CS_SLOT_OUT);
+    // n_selected and the rows of `selected` are fetched below, as far as they were written
+    const PackPart thr_part = thr.in(thresholds, n_thresholds), gene_count = res.out(out.gene_count, n_runs),
+                   best = res.out(out.best_allele, n_runs), best_count = res.out(out.best_count, n_runs),
+                   mask = res.out(out.mask, n_runs), nsel = res.out<uint32_t>(nullptr, CS_MAX_THRESHOLDS),
+                   sel = res.out<int32_t>(nullptr, out.selected ? (size_t)n_runs * n_thresholds : 0);
     PGX_HIP(d_ws.alloc(g.bytes));
-    PGX_HIP(d_start.alloc(((size_t)n_runs + 1) * 4));
-    PGX_HIP(d_gene.alloc(per_run));
-    PGX_HIP(d_thr.alloc(CS_MAX_THRESHOLDS * 4));
-    PGX_HIP(d_out.alloc(lay.off));
-    PGX_HIP(hipMemcpyAsync(d_start.p, run_start, ((size_t)n_runs + 1) * 4, hipMemcpyHostToDevice, stream));
-    if (gene_of_run) PGX_HIP(hipMemcpyAsync(d_gene.p, gene_of_run, per_run, hipMemcpyHostToDevice, stream));
-    PGX_HIP(hipMemcpyAsync(d_thr.p, thresholds, (size_t)n_thresholds * 4, hipMemcpyHostToDevice, stream));
-    char *o = (char *)d_out.p;
-    SelectOut dev;
-    dev.gene_count = out.gene_count ? (uint32_t *)(o + off_gene) : nullptr;
-    dev.best_allele = out.best_allele ? (int32_t *)(o + off_best) : nullptr;
-    dev.best_count = out.best_count ? (uint32_t *)(o + off_bcount) : nullptr;
-    dev.mask = out.mask ? (uint32_t *)(o + off_mask) : nullptr;
-    dev.selected = out.selected ? (int32_t *)(o + off_sel) : nullptr;
-    dev.n_selected = (out.selected || out.n_selected) ? (uint32_t *)(o + off_nsel) : nullptr;
-    rc = select_run(ctx, d_abits.as<uint64_t>(), n_alleles, gene_of_run ? d_gbits.as<uint64_t>() : nullptr, n_genes, n_genomes,
-                    d_start.as<uint32_t>(), n_runs, gene_of_run ? d_gene.as<int32_t>() : nullptr, d_thr.as<uint32_t>(),
-                    n_thresholds, dev, d_ws.p, g.bytes, stream);
+    PGX_HIP(thr.alloc());
+    PGX_HIP(res.alloc());
+    PGX_HIP(thr.upload(ctx->stream));
+    const SelectOut dev = {res.dev_if(out.gene_count, gene_count), res.dev_if(out.best_allele, best),
+                           res.dev_if(out.best_count, best_count), res.dev_if(out.mask, mask), res.dev_if(out.selected, sel),
+                           (out.selected || out.n_selected) ? res.dev<uint32_t>(nsel) : nullptr};
+    rc = select_run(ctx, in.d_abits, n_alleles, in.d_gbits, n_genes, n_genomes, in.d_run_start, n_runs, in.d_gene_of_run,
+                    thr.dev<uint32_t>(thr_part), n_thresholds, dev, d_ws.p, g.bytes, ctx->stream);
     if (rc != PGX_OK) return rc;
-    auto down = [&](void *dst, const void *src, size_t bytes) {
-        return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream) : hipSuccess;
-    };
-    PGX_HIP(down(out.gene_count, o + off_gene, per_run));
-    PGX_HIP(down(out.best_allele, o + off_best, per_run));
-    PGX_HIP(down(out.best_count, o + off_bcount, per_run));
-    PGX_HIP(down(out.mask, o + off_mask, per_run));
+    PGX_HIP(res.download(ctx->stream));
     uint32_t n_sel[CS_MAX_THRESHOLDS] = {0};
-    if (dev.n_selected) {                                     // the rows of `selected` come down as far as they were written
-        PGX_HIP(hipMemcpyAsync(n_sel, dev.n_selected, (size_t)n_thresholds * 4, hipMemcpyDeviceToHost, stream));
-        PGX_HIP(hipStreamSynchronize(stream));
+    if (dev.n_selected) {
+        PGX_HIP(res.download(nsel, 0, n_thresholds, n_sel, ctx->stream));
+        PGX_HIP(hipStreamSynchronize(ctx->stream));
         if (out.n_selected) memcpy(out.n_selected, n_sel, (size_t)n_thresholds * 4);
     }
     for (uint32_t t = 0; out.selected && t < n_thresholds; ++t)
-        PGX_HIP(down(out.selected + (size_t)t * n_runs, o + off_sel + (size_t)t * per_run, (size_t)std::min(n_sel[t], n_runs) * 4));
-    PGX_HIP(hipStreamSynchronize(stream));
+        PGX_HIP(res.download(sel, (size_t)t * n_runs, std::min(n_sel[t], n_runs), out.selected + (size_t)t * n_runs, ctx->stream));
+    PGX_HIP(hipStreamSynchronize(ctx->stream));
     return PGX_OK;
 }
 

@@ -405,31 +405,22 @@ int svm_host(pgx_ctx *ctx, const int32_t *rows, const int32_t *genomes, uint64_t
     PGX_REQUIRE(dup == 0, "duplicate coordinates: not a 0/1 table");
     const SvmGeom g = make_geom(n_rows, n_genomes, n_masks);
     const size_t n = n_genomes, P = n_problems;
-    WsLayout in, out;
-    const size_t i_masks = in.take((size_t)n_masks * g.stride * 8), i_mask_of = in.take(P * 4), i_C = in.take(P * 8),
-                 i_mult = in.take(P * n * 2), i_labels = in.take(n);
-    const size_t o_beta = out.take(P * n * 8), o_coef = out.take(P * n_rows * 8), o_icpt = out.take(P * 8),
-                 o_dec = out.take(P * n * 8), o_steps = out.take(P * 4);
-    DevBuf d_ws(ctx, SV_SLOT_WS), d_in(ctx, SV_SLOT_IN), d_out(ctx, SV_SLOT_OUT);
+    DevBuf d_ws(ctx, SV_SLOT_WS);
+    DevPack in(ctx, SV_SLOT_IN), res(ctx, SV_SLOT_OUT);
+    const PackPart i_masks = in.in(masks, (size_t)n_masks * g.stride), i_mask_of = in.in(mask_of, P), i_C = in.in(C, P),
+                   i_mult = in.in(mult, P * n), i_labels = in.in(labels, n);
+    const PackPart o_beta = res.out(out_beta, P * n), o_coef = res.out(out_coef, P * n_rows), o_icpt = res.out(out_intercept, P),
+                   o_dec = res.out(out_decision, P * n), o_steps = res.out(out_steps, P);
     PGX_HIP(d_ws.alloc(g.bytes));
-    PGX_HIP(d_in.alloc(in.off));
-    PGX_HIP(d_out.alloc(out.off));
-    char *pi = (char *)d_in.p, *po = (char *)d_out.p;
-    PGX_HIP(hipMemcpyAsync(pi + i_masks, masks, (size_t)n_masks * g.stride * 8, hipMemcpyHostToDevice, stream));
-    PGX_HIP(hipMemcpyAsync(pi + i_mask_of, mask_of, P * 4, hipMemcpyHostToDevice, stream));
-    PGX_HIP(hipMemcpyAsync(pi + i_C, C, P * 8, hipMemcpyHostToDevice, stream));
-    PGX_HIP(hipMemcpyAsync(pi + i_mult, mult, P * n * 2, hipMemcpyHostToDevice, stream));
-    PGX_HIP(hipMemcpyAsync(pi + i_labels, labels, n, hipMemcpyHostToDevice, stream));
-    rc = svm_run(ctx, d_bits.as<uint64_t>(), n_rows, n_genomes, (const uint64_t *)(pi + i_masks), n_masks,
-                 (const int32_t *)(pi + i_mask_of), (const double *)(pi + i_C), (const uint16_t *)(pi + i_mult), n_problems,
-                 (const uint8_t *)(pi + i_labels), tol, max_steps, (double *)(po + o_beta), (double *)(po + o_coef),
-                 (double *)(po + o_icpt), (double *)(po + o_dec), (uint32_t *)(po + o_steps), d_ws.p, g.bytes, stream);
+    PGX_HIP(in.alloc());
+    PGX_HIP(res.alloc());
+    PGX_HIP(in.upload(stream));
+    rc = svm_run(ctx, d_bits.as<uint64_t>(), n_rows, n_genomes, in.dev<uint64_t>(i_masks), n_masks, in.dev<int32_t>(i_mask_of),
+                 in.dev<double>(i_C), in.dev<uint16_t>(i_mult), n_problems, in.dev<uint8_t>(i_labels), tol, max_steps,
+                 res.dev<double>(o_beta), res.dev<double>(o_coef), res.dev<double>(o_icpt), res.dev<double>(o_dec),
+                 res.dev<uint32_t>(o_steps), d_ws.p, g.bytes, stream);
     if (rc != PGX_OK) return rc;
-    PGX_HIP(hipMemcpyAsync(out_beta, po + o_beta, P * n * 8, hipMemcpyDeviceToHost, stream));
-    PGX_HIP(hipMemcpyAsync(out_coef, po + o_coef, P * n_rows * 8, hipMemcpyDeviceToHost, stream));
-    PGX_HIP(hipMemcpyAsync(out_intercept, po + o_icpt, P * 8, hipMemcpyDeviceToHost, stream));
-    PGX_HIP(hipMemcpyAsync(out_decision, po + o_dec, P * n * 8, hipMemcpyDeviceToHost, stream));
-    PGX_HIP(hipMemcpyAsync(out_steps, po + o_steps, P * 4, hipMemcpyDeviceToHost, stream));
+    PGX_HIP(res.download(stream));
     PGX_HIP(hipStreamSynchronize(stream));
     return PGX_OK;
 }

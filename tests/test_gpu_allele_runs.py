@@ -229,3 +229,31 @@ def test_tables_of_build_cds_pangenome_are_consistent_until_an_entry_is_removed(
         from_file = pangenome.validate_gene_table(str(tmp_path / 'out' / 'T_strain_by_gene.npz'),
                                                   str(tmp_path / 'out' / 'T_strain_by_allele.npz'), ctx=gpu_ctx)
     assert from_file == 0
+
+
+@pytest.mark.parametrize('n_genomes', (3, 70))
+def test_host_entry_serves_every_output_alone_with_and_without_a_gene_table(n_genomes, gpu_ctx):
+    """One output per call: each comes back through its own part of the result buffer, and diff_per_run / diff_per_genome
+    alone take their diff bitmap from the workspace."""
+    rng = np.random.default_rng(n_genomes)
+    n_alleles, run_start = 13, np.array([0, 2, 2, 7, 12], dtype=np.uint32)       # an empty run, a last row in no run
+    n_runs = run_start.size - 1
+    A = rng.random((n_alleles, n_genomes)) < 0.4
+    derived = model.runs(A, run_start)['derived']
+    G = np.stack([~derived[0], derived[2], rng.random(n_genomes) < 0.5])         # gene 0 differs in every genome
+    gene_of_run = np.array([0, -1, 1, 2], dtype=np.int32)
+    (ar, ac), (gr, gc) = coo(A), coo(G)
+    with_genes, without = model.runs(A, run_start, G, gene_of_run), model.runs(A, run_start)
+    assert with_genes['diff'].any()
+    for k in OUTPUTS:
+        got, dups = gpu_ctx.allele_runs(ar, ac, n_alleles, n_genomes, run_start, gr, gc, G.shape[0], gene_of_run, want=(k,))
+        assert dups == (0, 0) and list(got) == [k]
+        model.assert_equal(got, {k: with_genes[k]}, n_runs)
+        got, dups = gpu_ctx.allele_runs(ar, ac, n_alleles, n_genomes, run_start, want=(k,))
+        assert dups == (0, 0) and list(got) == [k]
+        model.assert_equal(got, {k: without[k]}, n_runs)
+    got, _ = gpu_ctx.allele_runs(ar, ac, n_alleles, n_genomes, run_start, gr, gc, G.shape[0], gene_of_run,
+                                 want=('diff_per_run', 'diff_per_genome'))
+    model.assert_equal(got, {k: with_genes[k] for k in ('diff_per_run', 'diff_per_genome')}, n_runs)
+    out, dups = gpu_ctx.allele_runs(ar, ac, n_alleles, n_genomes, [0], want=())  # no runs and nothing asked for
+    assert out == {} and dups == (0, 0)

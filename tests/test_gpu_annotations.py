@@ -270,3 +270,15 @@ def test_extract_annotations_on_a_generated_names_file(gpu_ctx, tmp_path, capsys
         assert capsys.readouterr().out == printed_h
         assert dict(pg.ANNOTATION_PATH_COUNTS) == {'extract_device': 1}
         assert open(out_d, 'rb').read() == open(out_h, 'rb').read() and len(open(out_h, 'rb').read()) > 1000
+
+
+@pytest.mark.parametrize('flags', FLAGS)
+@pytest.mark.parametrize('n_rows', (3, 70))
+def test_rows_that_are_all_empty(n_rows, flags, gpu_ctx):
+    """no id at all: nothing goes up but the offsets, `keep` has no entry, and every run's winner is its first row"""
+    rows = [[] for _ in range(n_rows)]
+    for run_off in ([0, n_rows], [0, 1, n_rows], list(range(n_rows + 1))):
+        run_off = np.array(run_off, dtype=np.uint32)
+        keep, winner, votes, differs = check_vote(gpu_ctx, rows, run_off, flags, model.vote(rows, run_off))
+        assert keep.size == 0 and winner.tolist() == run_off[:-1].tolist() and not differs.any()
+        assert votes.tolist() == np.diff(run_off).tolist()

@@ -302,3 +302,72 @@ def test_calls_in_a_row_reuse_the_workspace(gpu_ctx):
         ml_pipelines.contingency_tables_from_sparse(coo, fx['targets'], ctx=gpu_ctx)
     torch.cuda.synchronize()
     assert torch.cuda.mem_get_info()[0] == free_before
+
+
+# -- the host entries' transfers ---------------------------------------------------------------------------------------
+def pack_targets(targets):
+    """uint64 [n_targets, words] of bool [n_targets, n_selected]: bit j & 63 of word j >> 6 = selected genome j"""
+    targets = np.asarray(targets, dtype=bool)
+    words = max(1, (targets.shape[1] + 63) // 64)
+    bits = np.zeros((targets.shape[0], words * 64), dtype=bool)
+    bits[:, :targets.shape[1]] = targets
+    return np.packbits(bits, axis=1, bitorder='little').view('<u8').astype(np.uint64).reshape(targets.shape[0], words)
+
+
+def small_table(n_genomes):
+    """Seven rows of which only four can differ (so n_blocks < n_rows), the two empty ones among them."""
+    rng = np.random.default_rng(n_genomes)
+    base = rng.random((3, n_genomes)) < 0.5
+    base[:, 0], base[0, -1], base[1, -1] = True, True, False
+    X = np.vstack([base[[0, 1, 0, 2, 1]], np.zeros((2, n_genomes), dtype=bool)])[[5, 0, 1, 2, 6, 3, 4]]
+    return X
+
+
+@pytest.mark.parametrize('n_genomes', (3, 70))
+def test_small_tables_through_both_host_entries(n_genomes, gpu_ctx):
+    rng = np.random.default_rng(100 + n_genomes)
+    X = small_table(n_genomes)
+    n_rows = X.shape[0]
+    r, c = (a.astype(np.int32) for a in np.nonzero(X))
+    token = gpu_ctx.bitmap_from_clusters(r, np.arange(r.size), c.astype(np.uint32), np.arange(n_genomes), n_rows, n_genomes)
+    perm = rng.permutation(n_rows).astype(np.int32)
+    col_map = rng.permutation(n_genomes)[:max(2, n_genomes // 2)].astype(np.int32)
+    for cmap in (None, col_map):
+        for name, table, call in (('upload', X, lambda **kw: gpu_ctx.assoc(r, c, n_rows, n_genomes, **kw)[0]),
+                                  ('resident', X[perm], lambda **kw: gpu_ctx.assoc_resident(token, perm, n_genomes, **kw))):
+            sub = table if cmap is None else table[:, cmap]
+            targets = rng.random((2, sub.shape[1])) < 0.5
+            block_of_row, rep_row = assoc_model.blocks(sub)
+            assert rep_row.size < n_rows
+            for masks, blocks in ((None, False), (None, True), (targets, False), (targets, True)):
+                out = call(col_map=cmap, masks=None if masks is None else pack_targets(masks), blocks=blocks)
+                what = (name, cmap is not None, masks is not None, blocks)
+                assert np.array_equal(out['incidence'], sub.sum(axis=1)), what
+                if masks is None:
+                    assert out['tp'].shape == (0, n_rows), what
+                else:
+                    assert np.array_equal(out['tp'], (sub[None, :, :] & masks[:, None, :]).sum(axis=2)), what
+                if blocks:
+                    assert np.array_equal(out['block_of_row'], block_of_row) and np.array_equal(out['rep_row'], rep_row), what
+                else:
+                    assert out['block_of_row'] is None and out['rep_row'] is None, what
+
+
+def test_host_entry_leaves_rep_row_behind_n_blocks_as_the_caller_had_it(gpu_ctx):
+    import ctypes as C
+    from pangenomix_amd import _native
+    lib, P, h = _native.lib(), _native._ptr, gpu_ctx._h
+    X = small_table(3)
+    n_rows = X.shape[0]
+    block_of_row, rep_row = assoc_model.blocks(X)
+    r, c = (a.astype(np.int32) for a in np.nonzero(X))
+    sentinel = 0x5C5C5C5C
+    inc = np.full(n_rows, sentinel, dtype=np.uint32)
+    block, rep = np.full(n_rows, sentinel, dtype=np.int32), np.full(n_rows, sentinel, dtype=np.int32)
+    n_blocks, dup = C.c_uint32(77), C.c_uint64(77)
+    rc = lib.pgx_assoc(h, P(r), P(c), r.size, n_rows, 3, None, 3, None, 0, _native.ASSOC_BLOCKS, None, P(inc), P(block), P(rep),
+                       C.byref(n_blocks), C.byref(dup))
+    assert rc == 0 and dup.value == 0 and n_blocks.value == rep_row.size < n_rows
+    assert np.array_equal(inc, X.sum(axis=1)) and np.array_equal(block, block_of_row)
+    assert np.array_equal(rep[:rep_row.size], rep_row)
+    assert (rep[rep_row.size:] == sentinel).all(), 'rep_row was written behind n_blocks'

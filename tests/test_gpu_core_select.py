@@ -361,3 +361,54 @@ def test_both_workflows_on_the_files_build_cds_pangenome_wrote(gpu_ctx, tmp_path
     captured(cg.filter_sequences, files['faa'], names, want)
     assert error is None and open(got, 'rb').read() == open(want, 'rb').read() != b''
     assert open(got, 'rb').read().count(b'>') == len(names)
+
+
+# -- the host entry's transfers ----------------------------------------------------------------------------------------
+def small_case(n_genomes):
+    """Five runs (one empty, one without a gene row) and thresholds that select none, some and all of the eligible runs."""
+    rng = np.random.default_rng(n_genomes)
+    A = rng.random((12, n_genomes)) < 0.5
+    A[0] = True
+    run_start = np.array([0, 2, 2, 5, 9, 12], dtype=np.uint32)
+    G = np.zeros((3, n_genomes), dtype=bool)
+    G[0], G[1, :2], G[2, :1] = True, True, True
+    gene_of_run = np.array([0, 1, 1, -1, 2], dtype=np.int32)
+    thresholds = np.array([2 ** 32 - 1, 2, 0, n_genomes], dtype=np.uint32)
+    return A, run_start, thresholds, G, gene_of_run
+
+
+@pytest.mark.parametrize('n_genomes', (3, 70))
+def test_host_entry_with_rows_of_selected_that_are_empty_short_and_alone(n_genomes, gpu_ctx):
+    A, run_start, thresholds, G, gene_of_run = small_case(n_genomes)
+    n_runs = run_start.size - 1
+    want = model.select(A, run_start, thresholds, G, gene_of_run)
+    sizes = [s.size for s in want['selected']]
+    assert sizes[0] == 0 and 0 < sizes[1] < sizes[2] < n_runs and sizes[3] == 1
+    model.assert_equal(run_host(gpu_ctx, A, run_start, thresholds, G, gene_of_run), want, OUTPUTS)
+    for keys in (('mask',), ('selected',), ('n_selected',), ('gene_count',)):
+        got = run_host(gpu_ctx, A, run_start, thresholds, G, gene_of_run, want=keys)
+        assert set(keys) <= set(got) <= set(keys) | {'n_selected'}
+        model.assert_equal(got, want)
+    free = model.select(A, run_start, thresholds)                            # no gene table
+    for keys in (OUTPUTS, ('mask',), ('selected',)):
+        model.assert_equal(run_host(gpu_ctx, A, run_start, thresholds, want=keys), free)
+
+
+def test_host_entry_leaves_selected_behind_n_selected_as_the_caller_had_it(gpu_ctx):
+    lib, P, h = _native.lib(), _native._ptr, gpu_ctx._h
+    A, run_start, thresholds, G, gene_of_run = small_case(3)
+    n_runs, n_thr = run_start.size - 1, thresholds.size
+    want = model.select(A, run_start, thresholds, G, gene_of_run)
+    (ar, ac), (gr, gc) = coo(A), coo(G)
+    sentinel = 0x5C5C5C5C
+    selected = np.full((n_thr, n_runs), sentinel, dtype=np.int32)
+    n_selected = np.full(n_thr, sentinel, dtype=np.uint32)
+    dup = np.zeros(2, dtype=np.uint64)
+    rc = lib.pgx_core_select(h, P(ar), P(ac), ar.size, A.shape[0], P(gr), P(gc), gr.size, G.shape[0], A.shape[1], P(run_start),
+                             n_runs, P(gene_of_run), P(thresholds), n_thr, None, None, None, None, P(selected), P(n_selected),
+                             P(dup))
+    assert rc == 0 and dup.tolist() == [0, 0]
+    assert n_selected.tolist() == [s.size for s in want['selected']]
+    for t, sel in enumerate(want['selected']):
+        assert selected[t, :sel.size].tolist() == sel.tolist()
+        assert (selected[t, sel.size:] == sentinel).all(), 'row %d was written behind n_selected' % t

@@ -180,3 +180,20 @@ def test_fcd_match_dev_does_not_allocate_and_checks_its_sizes(gpu_ctx):
     assert int(d_total.numpy(np.uint64)[0]) == 0
     for g in (ws, d_match, d_overlap, d_total):
         g.assert_guards_intact()
+
+
+@pytest.mark.parametrize('shape', ((5, 3), (70, 70)))
+def test_lists_with_an_empty_concept(shape, gpu_ctx):
+    """a concept without rows, one without columns and one without either, in both lists and in every position: their
+    index arrays take no room in the upload, and they overlap nothing"""
+    n_rows, n_cols = shape
+    full = (tuple(range(n_rows)), tuple(range(n_cols)))
+    edge = ((n_rows - 1, 0), (n_cols - 1,))
+    F1 = [((), (0, 1)), full, ((1, 2), ()), edge, ((), ())]
+    F2 = [edge, ((), ()), full, ((0,), ())]
+    for A, B in ((F1, F2), (F2, F1), (F1[:1], F2), (F1, F2[1:2])):
+        O = sim.overlaps(A, B, shape)
+        want = sim.pairing(O)
+        match, overlap, total = fcd.match_concept_lists(A, B, shape, ctx=gpu_ctx)
+        assert np.array_equal(match, want[0]) and np.array_equal(overlap, want[1]) and total == want[2]
+        assert np.array_equal(fcd.concept_overlaps(A, B, shape, ctx=gpu_ctx), O)

@@ -418,3 +418,12 @@ def test_builders_equal_the_reference_on_the_first_fixtures(tag, gpu_ctx, tmp_pa
 
 def test_builders_equal_the_host_path_on_generated_genomes(gpu_ctx, tmp_path, capsys):
     model.compare_with_host_path(gpu_ctx, tmp_path, capsys)
+
+
+@pytest.mark.parametrize('n', (1, 3, 70))
+def test_cut_windows_that_are_all_empty(n, gpu_ctx):
+    """every length 0 on a text that is not empty: no output byte, the offsets all 0, no window bad"""
+    rng = np.random.default_rng(n)
+    text = letters(rng, 40)
+    out, off, bad = check_cut(gpu_ctx, text, rng.integers(0, 41, n).tolist(), [0] * n, rng.integers(0, 2, n).tolist())
+    assert len(bytes(out)) == 0 and not np.asarray(off).any() and not np.asarray(bad).any()
