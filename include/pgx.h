@@ -885,6 +885,71 @@ int pgx_annot_vote_dev(pgx_ctx *ctx, const int32_t *d_tok, const uint64_t *d_row
                        const uint32_t *d_run_off, uint32_t n_runs, uint32_t flags, uint8_t *d_keep, int32_t *d_winner,
                        uint32_t *d_votes, uint8_t *d_differs, void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* Shortest-path lengths from many sources to many targets of a directed graph: the device step of build_resistome and of
+ * the drug-class terms of generate_probable_hits_from_annotations (reference amr.py:289-349 and :150-165, one nx.has_path or
+ * nx.shortest_path per pair). The successors of node v are succ[succ_off[v] .. succ_off[v + 1]) (n_nodes + 1 offsets,
+ * succ_off[0] = 0); self-loops, parallel edges and cycles are legal; sources and targets are node ids and may repeat, which
+ * gives repeated rows or columns.
+ *   len[s * n_targets + t] = the number of NODES on a shortest directed path from sources[s] to targets[t]: 1 when they are
+ *                            the same node, 0 when there is no path (what len(nx.shortest_path(...)) returns, 0 for no path)
+ *   rounds                 = 1 + the largest number of edges on a shortest path from ANY node to a target it reaches: the
+ *                            rounds the device ran, the last one being the one that changed nothing
+ * Every node holds a bit mask of the targets it reaches; a round pulls the successors' masks of the previous round into a
+ * second buffer, so a bit that appears in round k stands for a path of k + 1 nodes. No atomics: both are functions of the
+ * input alone and the same input gives the same bytes on every call.
+ * n_nodes >= 2^24, 2^31 edges or more, n_nodes x ceil(n_targets / 64) >= 2^28, n_sources x n_targets >= 2^31, offsets that
+ * decrease or do not start at 0, a successor, source or target outside [0, n_nodes) (host entry) and too small a workspace
+ * fail with PGX_ERR_INVALID before anything is launched or written. n_sources = 0 or n_targets = 0 does nothing: no output
+ * is written, out_rounds included.
+ *   pgx_graph_reach      HOST pointers; out_rounds may be NULL; the device buffers stay in the context between calls
+ *   pgx_graph_reach_dev  the caller's DEVICE pointers (4-byte aligned), n_edges given by the caller, d_out_rounds (one
+ *                        uint32, may be NULL) and workspace (pgx_graph_reach_workspace_bytes(), 16-byte aligned; 0 for sizes
+ *                        that are refused). Plain launches on `stream`, which is synchronised once per round -- the host
+ *                        reads one word to learn whether anything changed -- and at the end; inputs are not written, nothing
+ *                        outside the outputs and the workspace is. Offsets and ids are not checked: successor lists are
+ *                        clamped into [0, n_edges) and an id that is not a node is skipped (as a successor it leads nowhere,
+ *                        as a target nothing reaches it, as a source it reaches nothing), so nothing outside the caller's
+ *                        buffers is touched, the result for broken offsets being unspecified. */
+size_t pgx_graph_reach_workspace_bytes(uint32_t n_nodes, uint32_t n_targets, uint32_t n_sources);
+int pgx_graph_reach(pgx_ctx *ctx, const uint32_t *succ_off, const uint32_t *succ, uint32_t n_nodes, const uint32_t *targets,
+                    uint32_t n_targets, const uint32_t *sources, uint32_t n_sources, uint32_t *out_len, uint32_t *out_rounds);
+int pgx_graph_reach_dev(pgx_ctx *ctx, const uint32_t *d_succ_off, const uint32_t *d_succ, uint32_t n_nodes, uint64_t n_edges,
+                        const uint32_t *d_targets, uint32_t n_targets, const uint32_t *d_sources, uint32_t n_sources,
+                        uint32_t *d_out_len, uint32_t *d_out_rounds, void *d_workspace, size_t workspace_bytes, void *stream);
+
+/* Which of n_terms short patterns occur in each of n short strings: the device step of
+ * generate_probable_hits_from_annotations (reference amr.py:196-230, Python's `in` for every annotation, drug and term).
+ * String i is the length[i] bytes of `text` at start[i] (the windows of pgx_prox_cut: zero-length windows are legal, windows
+ * may overlap or repeat); term t is the bytes terms[term_off[t] .. term_off[t + 1]) (n_terms + 1 offsets, term_off[0] = 0).
+ *   bit (t & 63) of out_mask[i * W + (t >> 6)], W = ceil(n_terms / 64), is set iff term t occurs as a contiguous substring
+ *   of string i; bits at or beyond n_terms are zero. The empty term occurs in every string, the empty one included.
+ * With PGX_TERM_FOLD_ASCII the bytes 'A'-'Z' (0x41-0x5A) of strings and terms are compared as 'a'-'z'; no other byte is
+ * changed: '@', '[', '`', '{' and bytes >= 0x80 are compared as they are. Every match is decided by a byte compare and no
+ * atomics are used: the same input gives the same bytes on every call.
+ * At most PGX_TERM_MAX_TERMS terms of PGX_TERM_MAX_BYTES bytes in all (they are kept in LDS). More than that, n >= 2^24,
+ * text_bytes >= 2^32, unknown flags, offsets that decrease or do not start at 0 and a window that leaves [0, text_bytes)
+ * (host entry) fail with PGX_ERR_INVALID before anything is launched or written. n = 0 or n_terms = 0 does nothing (there
+ * are no words to write).
+ *   pgx_term_scan      HOST pointers; the device buffers stay in the context between calls
+ *   pgx_term_scan_dev  the caller's DEVICE pointers (d_start and d_out_mask 8-byte aligned, d_length and d_term_off 4-byte
+ *                      aligned; text and terms may start at any address), term_bytes given by the caller. One launch on
+ *                      `stream`, which is then synchronised; no workspace; inputs are not written, nothing outside
+ *                      d_out_mask is. Windows and offsets are not checked: a window is clamped into [0, text_bytes) (cut
+ *                      short at its end), term offsets into [0, term_bytes], and a term that ends before it starts is taken
+ *                      as empty, so nothing outside the caller's buffers is read.
+ * pgx_term_scan_group_bytes(): the bytes of a string the lanes that share it take per step (as start positions of matches;
+ * a match may run over the end of its step). */
+#define PGX_TERM_FOLD_ASCII 1u
+#define PGX_TERM_MAX_TERMS 512u
+#define PGX_TERM_MAX_BYTES 32768u
+uint32_t pgx_term_scan_group_bytes(void);
+int pgx_term_scan(pgx_ctx *ctx, const uint8_t *text, uint64_t text_bytes, const uint64_t *start, const uint32_t *length,
+                  uint32_t n, const uint8_t *terms, const uint32_t *term_off, uint32_t n_terms, uint32_t flags,
+                  uint64_t *out_mask);
+int pgx_term_scan_dev(pgx_ctx *ctx, const uint8_t *d_text, uint64_t text_bytes, const uint64_t *d_start,
+                      const uint32_t *d_length, uint32_t n, const uint8_t *d_terms, const uint32_t *d_term_off,
+                      uint32_t n_terms, uint64_t term_bytes, uint32_t flags, uint64_t *d_out_mask, void *stream);
+
 /* feature names (pangenome.py:1944-1969) as fixed-width zero-padded ASCII records (numpy 'S<width>'):
  * <prefix><cluster>[<variant><member>]; variant NULL = gene names */
 int pgx_format_labels(const char *prefix, const char *variant, const int32_t *cluster, const int32_t *member,

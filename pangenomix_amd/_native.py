@@ -74,6 +74,9 @@ DICT_NARROW_HASH = 1                   # PGX_DICT_NARROW_HASH
 PROX_NARROW_HASH = 1                   # PGX_PROX_NARROW_HASH
 ANNOT_NARROW_HASH = 1                  # PGX_ANNOT_NARROW_HASH
 ASSOC_NARROW_HASH = 4                  # PGX_ASSOC_NARROW_HASH
+TERM_FOLD_ASCII = 1                    # PGX_TERM_FOLD_ASCII
+TERM_MAX_TERMS = 512                   # PGX_TERM_MAX_TERMS
+TERM_MAX_BYTES = 32768                 # PGX_TERM_MAX_BYTES
 
 
 # every symbol include/pgx.h declares: (restype, argtypes)
@@ -207,6 +210,14 @@ SIGNATURES = {
     'pgx_annot_vote': (C.c_int, [_P, _P, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32, _P, _P, _P, _P]),
     'pgx_annot_vote_dev': (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint64, _P, C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P,
                                      C.c_size_t, _P]),
+    'pgx_graph_reach_workspace_bytes': (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_uint32]),
+    'pgx_graph_reach': (C.c_int, [_P, _P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, _P, _P]),
+    'pgx_graph_reach_dev': (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint64, _P, C.c_uint32, _P, C.c_uint32, _P, _P, _P,
+                                      C.c_size_t, _P]),
+    'pgx_term_scan_group_bytes': (C.c_uint32, []),
+    'pgx_term_scan': (C.c_int, [_P, _P, C.c_uint64, _P, _P, C.c_uint32, _P, _P, C.c_uint32, C.c_uint32, _P]),
+    'pgx_term_scan_dev': (C.c_int, [_P, _P, C.c_uint64, _P, _P, C.c_uint32, _P, _P, C.c_uint32, C.c_uint64, C.c_uint32, _P,
+                                    _P]),
     'pgx_genome_sets_diff': (C.c_int, [_P, _P, _P, C.c_uint64, _P, _P, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P]),
     'pgx_genome_sets_diff_dev': (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P]),
     'pgx_cluster_greedy': (C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(ClusterParams), _P, _P, _P, _P,
@@ -1096,6 +1107,64 @@ class Context(object):
         """The same on device memory (raw device addresses; synchronises `stream`, see pgx.h)."""
         check(lib().pgx_annot_vote_dev(self._h, d_tok, d_row_off, int(n_rows), int(n_tokens), d_run_off, int(n_runs),
                                        int(flags), d_keep, d_winner, d_votes, d_differs, d_ws, int(ws_bytes), stream))
+
+    # -- path lengths in a directed graph, terms in strings (amr.build_resistome, generate_probable_hits_from_annotations) ---
+    def graph_reach(self, succ_off, succ, targets, sources, return_rounds=False):
+        """len uint32 [n_sources, n_targets]: the number of nodes on a shortest path from sources[s] to targets[t] of the
+        graph whose node v has the successors succ[succ_off[v]:succ_off[v + 1]]; 1 for the node itself, 0 for no path
+        (pgx.h: pgx_graph_reach). return_rounds: also the rounds the device ran."""
+        succ_off = np.ascontiguousarray(succ_off, dtype=np.uint32)
+        succ = np.ascontiguousarray(succ, dtype=np.uint32)
+        targets = np.ascontiguousarray(targets, dtype=np.uint32)
+        sources = np.ascontiguousarray(sources, dtype=np.uint32)
+        if succ_off.ndim != 1 or succ.ndim != 1 or targets.ndim != 1 or sources.ndim != 1 or succ_off.size < 1:
+            raise ValueError('succ_off must hold n_nodes + 1 entries; succ, targets and sources must be 1-D')
+        if int(succ_off[-1]) > succ.size:
+            raise ValueError('succ_off runs past the end of succ')
+        out = np.zeros((sources.size, targets.size), dtype=np.uint32)
+        rounds = C.c_uint32(0)
+        check(lib().pgx_graph_reach(self._h, _ptr(succ_off), _ptr(succ), succ_off.size - 1, _ptr(targets), targets.size,
+                                    _ptr(sources), sources.size, _ptr(out), C.byref(rounds)))
+        return (out, int(rounds.value)) if return_rounds else out
+
+    def graph_reach_workspace_bytes(self, n_nodes, n_targets, n_sources):
+        return int(lib().pgx_graph_reach_workspace_bytes(int(n_nodes), int(n_targets), int(n_sources)))
+
+    def graph_reach_dev(self, d_succ_off, d_succ, n_nodes, n_edges, d_targets, n_targets, d_sources, n_sources, d_out_len,
+                        d_out_rounds, d_ws, ws_bytes, stream=0):
+        """The same on device memory (raw device addresses, None for no rounds; synchronises `stream`, see pgx.h)."""
+        check(lib().pgx_graph_reach_dev(self._h, d_succ_off, d_succ, int(n_nodes), int(n_edges), d_targets, int(n_targets),
+                                        d_sources, int(n_sources), d_out_len, d_out_rounds, d_ws, int(ws_bytes), stream))
+
+    def term_scan(self, text, start, length, terms, term_off, flags=0):
+        """mask uint64 [n, ceil(n_terms / 64)]: bit t & 63 of word t >> 6 of row i is set iff the term
+        terms[term_off[t]:term_off[t + 1]] occurs in the length[i] bytes of `text` (bytes or a 1-D uint8 array) at start[i]
+        (pgx.h: pgx_term_scan). flags: TERM_FOLD_ASCII compares A-Z as a-z."""
+        if isinstance(text, (bytes, bytearray, memoryview)):
+            text = np.frombuffer(text, dtype=np.uint8)
+        if isinstance(terms, (bytes, bytearray, memoryview)):
+            terms = np.frombuffer(terms, dtype=np.uint8)
+        text = np.ascontiguousarray(text, dtype=np.uint8)
+        terms = np.ascontiguousarray(terms, dtype=np.uint8)
+        start = np.ascontiguousarray(start, dtype=np.uint64)
+        length = np.ascontiguousarray(length, dtype=np.uint32)
+        term_off = np.ascontiguousarray(term_off, dtype=np.uint32)
+        if text.ndim != 1 or terms.ndim != 1 or start.ndim != 1 or start.shape != length.shape or term_off.ndim != 1 \
+                or term_off.size < 1:
+            raise ValueError('text, terms, start and length must be 1-D and term_off hold n_terms + 1 entries')
+        if int(term_off[-1]) > terms.size:
+            raise ValueError('term_off runs past the end of terms')
+        n_terms = term_off.size - 1
+        mask = np.zeros((start.size, (n_terms + 63) // 64), dtype=np.uint64)
+        check(lib().pgx_term_scan(self._h, _ptr(text), text.size, _ptr(start), _ptr(length), start.size, _ptr(terms),
+                                  _ptr(term_off), n_terms, int(flags), _ptr(mask)))
+        return mask
+
+    def term_scan_dev(self, d_text, text_bytes, d_start, d_length, n, d_terms, d_term_off, n_terms, term_bytes, d_out_mask,
+                      flags=0, stream=0):
+        """The same on device memory (raw device addresses; synchronises `stream`, see pgx.h)."""
+        check(lib().pgx_term_scan_dev(self._h, d_text, int(text_bytes), d_start, d_length, int(n), d_terms, d_term_off,
+                                      int(n_terms), int(term_bytes), int(flags), d_out_mask, stream))
 
     def pan_core(self, bits, n_genes, perms):
         perms = np.ascontiguousarray(perms, dtype=np.int32)

@@ -72,6 +72,10 @@ enum DevSlot : int {        // pgx_ctx::arena, through DevBuf
     PX_SLOT_TEXT, PX_SLOT_WINDOWS, PX_SLOT_OUT, PX_SLOT_BLOB, PX_SLOT_RECORDS, PX_SLOT_WS, PX_SLOT_RESULT,
     // annot.hip: the ids, row and run offsets in one, the workspace, every result in one
     AN_SLOT_TOK, AN_SLOT_OFFSETS, AN_SLOT_WS, AN_SLOT_RESULT,
+    // reach.hip: the graph, targets and sources in one, the two mask buffers and the flag, the lengths
+    GR_SLOT_IN, GR_SLOT_WS, GR_SLOT_OUT,
+    // terms.hip: the text, the windows and the terms in one, the masks
+    TS_SLOT_TEXT, TS_SLOT_IN, TS_SLOT_OUT,
     DEV_SLOT_COUNT
 };
 enum HostSlot : int {       // pgx_ctx::host_scratch, through HostVec

@@ -163,3 +163,98 @@ def noncoding_set(n_genomes=400, seed=5, n_trna=60, rrna_lengths=(120, 1500, 290
     offsets = np.zeros(len(lens) + 1, dtype=np.uint64)
     np.cumsum(np.asarray(lens, dtype=np.uint64), out=offsets[1:])
     return np.frombuffer(b''.join(chunks), dtype=np.uint8), offsets, n_raw
+
+
+AMR_CLASS_NAMES = ('beta-lactam antibiotic', 'penam', 'monobactam', 'cephalosporin', 'carbapenem', 'aminoglycoside antibiotic',
+                   'fluoroquinolone antibiotic', 'lincosamide antibiotic', 'macrolide antibiotic', 'phenicol antibiotic',
+                   'nitrofuran antibiotic', 'tetracycline antibiotic', 'glycylcycline', 'diaminopyrimidine antibiotic',
+                   'sulfonamide antibiotic', 'glycopeptide antibiotic')
+
+
+def write_amr_case(outdir, class_aros, n_terms=300, n_hits=200, n_drugs=12, n_lines=2000, n_products=150, seed=0, name_every=3):
+    """Inputs of pangenomix_amd.amr in `outdir`: aro.obo -- ARO:1000001, ARO:1000003 with the sixteen drug classes
+    (`class_aros`, amr.DRUG_CLASS_AROS) and a tree of n_terms / 3 drugs and mixtures under them, n_terms * 2 / 3 resistance
+    determinants in families, some of which confer resistance to a drug or a class, are part of or regulate another --,
+    rgi.txt with n_hits rows (a few Loose, a few ORF_IDs twice) and annotations.tsv with n_lines lines of one to three of
+    n_products products, every name_every-th of which names a drug, a part of a mixture or a class, in mixed case, and every
+    seventh a class and a drug. Returns a dict: the three paths, `drugs`
+    ({name: ARO} of n_drugs drugs, every fourth a mixture keyed 'a/b'), `drug_to_aro` and `manual_annots`."""
+    rng = np.random.default_rng(seed)
+    pick = lambda seq: seq[int(rng.integers(0, len(seq)))]                      # noqa: E731
+    blocks, drug_tree, drug_names, mixtures, genes = [], list(class_aros), {}, [], ['ARO:3000000']
+
+    def term(aro, name, is_a, relationships=()):
+        blocks.append('[Term]\nid: %s\nname: %s\n' % (aro, name) + ''.join('is_a: %s ! x\n' % p for p in is_a) +
+                      ''.join('relationship: %s %s ! x\n' % r for r in relationships))
+    term('ARO:1000001', 'process or component of antibiotic biology or chemistry', [])
+    term('ARO:1000003', 'antibiotic molecule', ['ARO:1000001'])
+    term('ARO:3000000', 'determinant of antibiotic resistance', ['ARO:1000001'])
+    for aro, name in zip(class_aros, AMR_CLASS_NAMES):
+        term(aro, name, ['ARO:1000003'])
+    n_drug_terms = max(n_drugs + 4, n_terms // 3)
+    for i in range(n_drug_terms):
+        aro = 'ARO:%07d' % (4000000 + i)
+        if i % 9 == 8 and len(drug_names) >= 2:                                 # a mixture of two drugs
+            a, b = pick(list(drug_names)), pick(list(drug_names))
+            term(aro, 'mix%d' % i, ['ARO:1000003'], [('has_part', a), ('has_part', b)])
+            mixtures.append((aro, drug_names[a] + '/' + drug_names[b]))
+        else:
+            term(aro, 'drug%03dicin' % i, [pick(drug_tree)])
+            drug_tree.append(aro)
+            drug_names[aro] = 'drug%03dicin' % i
+    drugs = {}
+    singles = list(drug_names.items())
+    for k in range(n_drugs):
+        if k % 4 == 3 and mixtures:
+            aro, name = mixtures[k // 4 % len(mixtures)]
+        else:
+            aro, name = singles[int(rng.integers(0, len(singles)))]
+        drugs[name] = aro
+    of_interest = [aro for aro in drugs.values() if aro in drug_names] or list(drug_names)
+    families = []
+    for i in range(n_terms - n_drug_terms):
+        aro = 'ARO:%07d' % (5000000 + i)
+        rel = []
+        if rng.random() < 0.08:                                                 # half of them to a drug of interest
+            rel.append(('confers_resistance_to_antibiotic', pick(of_interest if rng.random() < 0.5 else list(drug_names))))
+        if rng.random() < 0.03:
+            rel.append(('confers_resistance_to_drug_class', pick(list(class_aros))))
+        if rng.random() < 0.05:
+            rel.append((pick(['part_of', 'regulates', 'participates_in']), pick(genes)))
+        if not families or rng.random() < 0.08:                                 # a new family, or a member of a recent one
+            parent = 'ARO:3000000'
+            families.append([aro])
+        else:
+            family = families[int(rng.integers(max(0, len(families) - 10), len(families)))]
+            parent = pick(family)
+            family.append(aro)
+        term(aro, 'det%d' % i, [parent], rel)
+        genes.append(aro)
+    with open(os.path.join(outdir, 'aro.obo'), 'w') as f:
+        f.write('format-version: 1.2\n\n' + '\n'.join(blocks) + '\n[Typedef]\nid: part_of\n')
+
+    drug_list = list(drugs)
+    with open(os.path.join(outdir, 'rgi.txt'), 'w') as f:
+        f.write('ORF_ID\tCut_Off\tBest_Hit_ARO\tARO\n')
+        for h in range(n_hits):
+            orf = 'Syn_C%dA%d' % (h // 3 if h % 17 else max(h // 3 - 2, 0), h % 3)   # every 17th: an earlier ORF_ID again
+            gene = pick(genes[1:])
+            f.write('%s\t%s\tdet\t%d\n' % (orf, 'Loose' if h % 11 == 5 else pick(['Strict', 'Perfect']), int(gene[4:])))
+    words = ['protein', 'Resistance', 'efflux pump', 'hydrolase', 'transporter', 'family', 'regulator', 'subunit A', 'kinase']
+    products = ['hypothetical protein']
+    for p in range(n_products - 1):
+        parts = [pick(words), pick(words)]
+        if p % name_every == 0:                                                 # names a drug of interest, a part, a class
+            drug = pick(drug_list)
+            parts.insert(1, pick([drug, drug.split('/')[0].upper(), pick(AMR_CLASS_NAMES).replace(' antibiotic', '').title()]))
+        if p % 7 == 0:
+            parts.append(pick(AMR_CLASS_NAMES).split()[0] + ' ' + pick(drug_list).split('/')[-1])
+        products.append(' '.join(parts) + ' %d' % p)
+    with open(os.path.join(outdir, 'annotations.tsv'), 'w') as f:
+        for i in range(n_lines):
+            feature = 'Syn_C%dA%d' % (i // 3, i % 3) if i % 5 else 'Syn_C%d' % (i // 3)
+            pool = products[:max(8, n_products // 10)] if i < n_hits else products   # the hits share a tenth of the products
+            f.write('\t'.join([feature] + [pick(pool) for _ in range(int(rng.integers(1, 4)))]) + '\n')
+    return {'obo': os.path.join(outdir, 'aro.obo'), 'rgi': os.path.join(outdir, 'rgi.txt'),
+            'annotations': os.path.join(outdir, 'annotations.tsv'), 'drugs': drugs,
+            'drug_to_aro': {drug_list[0]: genes[1]}, 'manual_annots': {drug_list[-1]: ['efflux pump', 'Kinase']}}
