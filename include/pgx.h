@@ -950,6 +950,72 @@ int pgx_term_scan_dev(pgx_ctx *ctx, const uint8_t *d_text, uint64_t text_bytes, 
                       const uint32_t *d_length, uint32_t n, const uint8_t *d_terms, const uint32_t *d_term_off,
                       uint32_t n_terms, uint64_t term_bytes, uint32_t flags, uint64_t *d_out_mask, void *stream);
 
+/* Exact grouping of fixed-width integer tuples: the device step of extract_primary_stnds and extract_mic_calls (reference
+ * amr_inference.py:222-347, one value_counts per organism and drug and one collections.Counter per organism).
+ * Record i is the k values cols[c * n + i], c = 0 .. k - 1 (column-major, n values per column); any int32 value is allowed.
+ * Two records are equal iff they agree in all k columns.
+ *   first[i]    = the smallest j with record j equal to record i
+ *   count[i]    = the number of records equal to record i when first[i] == i, and 0 otherwise
+ *   *n_distinct = the number of i with first[i] == i
+ * All three are functions of the input alone: the same input gives the same bytes on every call. first is a minimum over a
+ * set and count an integer sum; no atomic decides an order. Hashes only decide where to look -- a j is reported after all k
+ * columns have been compared. PGX_TUPLE_NARROW_HASH (a test seam) keeps only the low 3 bits of every hash: same results,
+ * every probe collides. k outside 1 .. PGX_TUPLE_MAX_COLUMNS, n >= 2^24, unknown flags and too small a workspace fail with
+ * PGX_ERR_INVALID before anything is launched or written. n = 0 sets *n_distinct to 0.
+ *   pgx_tuple_group      HOST pointers; the device buffers stay in the context between calls
+ *   pgx_tuple_group_dev  the caller's DEVICE pointers (4-byte aligned) and workspace (pgx_tuple_group_workspace_bytes(),
+ *                        16-byte aligned; 0 for sizes that are refused). Plain launches on `stream`, which is synchronised
+ *                        once at the end; inputs are not written, nothing outside the outputs and the workspace is. */
+#define PGX_TUPLE_NARROW_HASH 1u  /* keep only the low 3 bits of every hash: same results, every probe collides */
+#define PGX_TUPLE_MAX_COLUMNS 8u
+size_t pgx_tuple_group_workspace_bytes(uint32_t n, uint32_t k);
+int pgx_tuple_group(pgx_ctx *ctx, const int32_t *cols, uint32_t n, uint32_t k, uint32_t flags, int32_t *out_first,
+                    uint32_t *out_count, uint32_t *out_n_distinct);
+int pgx_tuple_group_dev(pgx_ctx *ctx, const int32_t *d_cols, uint32_t n, uint32_t k, uint32_t flags, int32_t *d_first,
+                        uint32_t *d_count, uint32_t *d_n_distinct, void *d_workspace, size_t workspace_bytes, void *stream);
+
+/* SIR inference: the body of infer_sir (reference amr_inference.py:27-100) for n rows at once.
+ * Case c (an organism x drug pair with reference MICs) has the class entries class_begin[c] .. class_begin[c + 1] (n_cases + 1
+ * offsets, class_begin[0] = 0, class_begin[n_cases] = n_entries), in the order mic_ranges[entry] iterates. Class entry e:
+ *   sir[e]   the code that is returned (>= 0);  role[e]  0 for 'susceptible', 1 for 'resistant', 2 for any other name
+ *   fvals[fl_begin[e] .. fl_begin[e + 1])  its numeric MICs, sorted, no NaN (n_entries + 1 offsets, from 0 to n_fvals)
+ *   tvals[tk_begin[e] .. tk_begin[e + 1])  the int32 codes of its string MICs, sorted (n_entries + 1 offsets, from 0 to n_tvals)
+ * Row i:
+ *   case[i]   its case, -1 for no case or no ranges
+ *   sign[i]   0 equality, 1 '<' or '<=', 2 '>' or '>=', 3 neither
+ *   combo[i]  the reference's is_likely_combo (0 or 1)
+ *   kind[i]   0: a string measurement whose code is token[i], -1 for a string that is in no list; 1: a float measurement
+ *             whose key is value[i], compared with ==, so that a NaN is never a member
+ *   value[i]  float(measurement_value); read only when combo[i] == 0 or kind[i] == 1
+ * A class entry TAKES a row when the row's key is a member of the entry's list (tvals for kind 0, fvals for kind 1) or, if
+ * combo[i] == 0, when (role == 0 or value >= min) and (role == 1 or value <= max), min the first and max the last of the
+ * entry's fvals, with IEEE comparisons (a NaN fails both).
+ *   sign 0:  out[i] = sir[e] of the first entry of the case, in case order, that takes the row: a range hit of an earlier
+ *            class beats a membership hit of a later one
+ *   sign 1:  only the case's first entry of role 0 is tried; sign 2: only its first entry of role 1
+ *   out[i] = -1 when no entry takes the row, the case is -1 or the sign is 3
+ *   out[i] = -2 ("needs the host") when the range test would be evaluated on an entry that has a string MIC or no fvals:
+ *            the reference raises TypeError or ValueError there
+ * One launch, no atomics: the same input gives the same bytes on every call. n >= 2^31, and 2^24 or more cases, class
+ * entries, fvals or tvals fail with PGX_ERR_INVALID before anything is launched or written, as do (host entry) offsets that
+ * decrease or do not run from 0 to the stated totals, a role above 2, a negative sir code and a run that is not sorted or
+ * holds a NaN. n = 0 does nothing.
+ *   pgx_mic_infer      HOST pointers; the device buffers stay in the context between calls
+ *   pgx_mic_infer_dev  the caller's DEVICE pointers (the doubles 8-byte aligned, the 32-bit arrays 4-byte aligned). One launch
+ *                      on `stream`, which is then synchronised; no workspace; inputs are not written, nothing outside d_out
+ *                      is. Offsets are not checked: every one is clamped to the array it points into and a case outside
+ *                      [0, n_cases) is taken as -1, so nothing outside the caller's buffers is read, the result for broken
+ *                      tables being unspecified. */
+int pgx_mic_infer(pgx_ctx *ctx, const uint32_t *class_begin, uint32_t n_cases, const int32_t *sir, const uint8_t *role,
+                  const uint32_t *fl_begin, const uint32_t *tk_begin, uint32_t n_entries, const double *fvals, uint32_t n_fvals,
+                  const int32_t *tvals, uint32_t n_tvals, const int32_t *row_case, const uint8_t *sign, const uint8_t *combo,
+                  const uint8_t *kind, const int32_t *token, const double *value, uint64_t n, int32_t *out);
+int pgx_mic_infer_dev(pgx_ctx *ctx, const uint32_t *d_class_begin, uint32_t n_cases, const int32_t *d_sir, const uint8_t *d_role,
+                      const uint32_t *d_fl_begin, const uint32_t *d_tk_begin, uint32_t n_entries, const double *d_fvals,
+                      uint32_t n_fvals, const int32_t *d_tvals, uint32_t n_tvals, const int32_t *d_case, const uint8_t *d_sign,
+                      const uint8_t *d_combo, const uint8_t *d_kind, const int32_t *d_token, const double *d_value, uint64_t n,
+                      int32_t *d_out, void *stream);
+
 /* feature names (pangenome.py:1944-1969) as fixed-width zero-padded ASCII records (numpy 'S<width>'):
  * <prefix><cluster>[<variant><member>]; variant NULL = gene names */
 int pgx_format_labels(const char *prefix, const char *variant, const int32_t *cluster, const int32_t *member,

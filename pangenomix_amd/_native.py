@@ -77,6 +77,8 @@ ASSOC_NARROW_HASH = 4                  # PGX_ASSOC_NARROW_HASH
 TERM_FOLD_ASCII = 1                    # PGX_TERM_FOLD_ASCII
 TERM_MAX_TERMS = 512                   # PGX_TERM_MAX_TERMS
 TERM_MAX_BYTES = 32768                 # PGX_TERM_MAX_BYTES
+TUPLE_NARROW_HASH = 1                  # PGX_TUPLE_NARROW_HASH
+TUPLE_MAX_COLUMNS = 8                  # PGX_TUPLE_MAX_COLUMNS
 
 
 # every symbol include/pgx.h declares: (restype, argtypes)
@@ -218,6 +220,13 @@ SIGNATURES = {
     'pgx_term_scan': (C.c_int, [_P, _P, C.c_uint64, _P, _P, C.c_uint32, _P, _P, C.c_uint32, C.c_uint32, _P]),
     'pgx_term_scan_dev': (C.c_int, [_P, _P, C.c_uint64, _P, _P, C.c_uint32, _P, _P, C.c_uint32, C.c_uint64, C.c_uint32, _P,
                                     _P]),
+    'pgx_tuple_group_workspace_bytes': (C.c_size_t, [C.c_uint32, C.c_uint32]),
+    'pgx_tuple_group': (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, _P]),
+    'pgx_tuple_group_dev': (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, _P, _P, C.c_size_t, _P]),
+    'pgx_mic_infer': (C.c_int, [_P, _P, C.c_uint32, _P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, _P, _P, _P, _P,
+                                _P, _P, C.c_uint64, _P]),
+    'pgx_mic_infer_dev': (C.c_int, [_P, _P, C.c_uint32, _P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, _P, _P, _P,
+                                    _P, _P, _P, C.c_uint64, _P, _P]),
     'pgx_genome_sets_diff': (C.c_int, [_P, _P, _P, C.c_uint64, _P, _P, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P]),
     'pgx_genome_sets_diff_dev': (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P]),
     'pgx_cluster_greedy': (C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(ClusterParams), _P, _P, _P, _P,
@@ -1165,6 +1174,55 @@ class Context(object):
         """The same on device memory (raw device addresses; synchronises `stream`, see pgx.h)."""
         check(lib().pgx_term_scan_dev(self._h, d_text, int(text_bytes), d_start, d_length, int(n), d_terms, d_term_off,
                                       int(n_terms), int(term_bytes), int(flags), d_out_mask, stream))
+
+    # -- equal integer tuples counted, SIR classes inferred from MICs (amr_inference) ------------------------------------------
+    def tuple_group(self, cols, flags=0):
+        """(first int32 [n], count uint32 [n], n_distinct) of the n records cols[:, i] of an int32 array [k, n]: the smallest
+        index of an equal record, and at that index how many records equal it, 0 elsewhere (pgx.h: pgx_tuple_group).
+        flags: TUPLE_NARROW_HASH, the test seam."""
+        cols = np.ascontiguousarray(cols, dtype=np.int32)
+        if cols.ndim != 2:
+            raise ValueError('cols must be [k, n]')
+        k, n = cols.shape
+        first = np.zeros(n, dtype=np.int32)
+        count = np.zeros(n, dtype=np.uint32)
+        distinct = C.c_uint32(0)
+        check(lib().pgx_tuple_group(self._h, _ptr(cols), n, k, int(flags), _ptr(first), _ptr(count), C.byref(distinct)))
+        return first, count, int(distinct.value)
+
+    def tuple_group_workspace_bytes(self, n, k):
+        return int(lib().pgx_tuple_group_workspace_bytes(int(n), int(k)))
+
+    def tuple_group_dev(self, d_cols, n, k, d_first, d_count, d_n_distinct, d_ws, ws_bytes, flags=0, stream=0):
+        """The same on device memory (raw device addresses; synchronises `stream`, see pgx.h)."""
+        check(lib().pgx_tuple_group_dev(self._h, d_cols, int(n), int(k), int(flags), d_first, d_count, d_n_distinct, d_ws,
+                                        int(ws_bytes), stream))
+
+    def mic_infer(self, class_begin, sir, role, fl_begin, tk_begin, fvals, tvals, case, sign, combo, kind, token, value):
+        """out int32 [n]: the sir code of the first class entry of case[i] that takes row i, -1 for none, -2 for a row the
+        host has to decide (pgx.h: pgx_mic_infer, where every array is described)."""
+        class_begin, fl_begin, tk_begin = (np.ascontiguousarray(a, dtype=np.uint32) for a in (class_begin, fl_begin, tk_begin))
+        sir, tvals, case, token = (np.ascontiguousarray(a, dtype=np.int32) for a in (sir, tvals, case, token))
+        role, sign, combo, kind = (np.ascontiguousarray(a, dtype=np.uint8) for a in (role, sign, combo, kind))
+        fvals, value = (np.ascontiguousarray(a, dtype=np.float64) for a in (fvals, value))
+        n_entries, n = sir.size, case.size
+        if class_begin.ndim != 1 or class_begin.size < 1 or fl_begin.shape != (n_entries + 1,) or fl_begin.shape != tk_begin.shape \
+                or role.shape != (n_entries,):
+            raise ValueError('class_begin must hold n_cases + 1, fl_begin and tk_begin n_entries + 1 and role n_entries entries')
+        if any(a.shape != (n,) for a in (sign, combo, kind, token, value)):
+            raise ValueError('case, sign, combo, kind, token and value must hold one entry per row')
+        out = np.zeros(n, dtype=np.int32)
+        check(lib().pgx_mic_infer(self._h, _ptr(class_begin), class_begin.size - 1, _ptr(sir), _ptr(role), _ptr(fl_begin),
+                                  _ptr(tk_begin), n_entries, _ptr(fvals), fvals.size, _ptr(tvals), tvals.size, _ptr(case),
+                                  _ptr(sign), _ptr(combo), _ptr(kind), _ptr(token), _ptr(value), n, _ptr(out)))
+        return out
+
+    def mic_infer_dev(self, d_class_begin, n_cases, d_sir, d_role, d_fl_begin, d_tk_begin, n_entries, d_fvals, n_fvals, d_tvals,
+                      n_tvals, d_case, d_sign, d_combo, d_kind, d_token, d_value, n, d_out, stream=0):
+        """The same on device memory (raw device addresses; synchronises `stream`, see pgx.h)."""
+        check(lib().pgx_mic_infer_dev(self._h, d_class_begin, int(n_cases), d_sir, d_role, d_fl_begin, d_tk_begin, int(n_entries),
+                                      d_fvals, int(n_fvals), d_tvals, int(n_tvals), d_case, d_sign, d_combo, d_kind, d_token,
+                                      d_value, int(n), d_out, stream))
 
     def pan_core(self, bits, n_genes, perms):
         perms = np.ascontiguousarray(perms, dtype=np.int32)

@@ -76,6 +76,9 @@ enum DevSlot : int {        // pgx_ctx::arena, through DevBuf
     GR_SLOT_IN, GR_SLOT_WS, GR_SLOT_OUT,
     // terms.hip: the text, the windows and the terms in one, the masks
     TS_SLOT_TEXT, TS_SLOT_IN, TS_SLOT_OUT,
+    // mic.hip: pgx_tuple_group (the columns, the workspace, every result in one), then pgx_mic_infer (the case tables in
+    // one, the row arrays in one, the codes)
+    TG_SLOT_IN, TG_SLOT_WS, TG_SLOT_OUT, MI_SLOT_TABLES, MI_SLOT_ROWS, MI_SLOT_OUT,
     DEV_SLOT_COUNT
 };
 enum HostSlot : int {       // pgx_ctx::host_scratch, through HostVec

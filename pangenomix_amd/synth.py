@@ -258,3 +258,77 @@ def write_amr_case(outdir, class_aros, n_terms=300, n_hits=200, n_drugs=12, n_li
     return {'obo': os.path.join(outdir, 'aro.obo'), 'rgi': os.path.join(outdir, 'rgi.txt'),
             'annotations': os.path.join(outdir, 'annotations.tsv'), 'drugs': drugs,
             'drug_to_aro': {drug_list[0]: genes[1]}, 'manual_annots': {drug_list[-1]: ['efflux pump', 'Kinase']}}
+
+
+PATRIC_AMR_COLUMNS = ('genome_id', 'genome_name', 'taxon_id', 'antibiotic', 'resistant_phenotype', 'measurement',
+                      'measurement_sign', 'measurement_value', 'measurement_unit', 'laboratory_typing_method',
+                      'laboratory_typing_method_version', 'laboratory_typing_platform', 'vendor', 'testing_standard',
+                      'testing_standard_year', 'computational_method', 'computational_method_version', 'source')
+
+
+def patric_amr_table(n_rows=1000000, n_orgs=8, genomes_per_org=2000, n_drugs=40, seed=11):
+    """(org_to_gids, df_amr): a table in the layout of PATRIC_genomes_AMR.txt for amr_inference, rows grouped by genome as
+    in the real file. `measurement` carries an inequality and `measurement_value` does not; both are strings, so that a
+    combination's 'a/b' stays what it is. Every organism x drug case has a susceptible and a resistant breakpoint on the
+    two-fold dilution series; a MIC at either end of the series is reported as '<=' or '>'; a tenth of the rows has a
+    phenotype and no measurement, a tenth a disk diffusion in mm; standards are clsi, eucast, 'missing' or null with
+    weights that differ by organism. A twentieth of the genomes belongs to no organism. Nulls of object columns are the
+    np.nan object, as pandas.read_csv leaves them."""
+    import pandas as pd
+    rng = np.random.default_rng(seed)
+    n_genomes = n_orgs * genomes_per_org
+    orgs = ['Genus%02d species%02d' % (o, o) for o in range(n_orgs)]
+    gids = np.array(['%d.%d' % (1000 + g // genomes_per_org, g % genomes_per_org) for g in range(n_genomes)], dtype=object)
+    owned = rng.random(n_genomes) >= 0.05
+    org_to_gids = {org: gids[o * genomes_per_org:(o + 1) * genomes_per_org][owned[o * genomes_per_org:(o + 1) * genomes_per_org]].tolist()
+                   for o, org in enumerate(orgs)}
+    drugs = np.array(['drug%02d' % d if d % 5 else 'drug%02d_partner%02d' % (d, d) for d in range(n_drugs)], dtype=object)
+    drugs[1], drugs[2] = 'polymyxin_b', 'nalidixic_acid'
+    is_combo = np.array([d % 5 == 0 for d in range(n_drugs)])
+    series = 2.0 ** np.arange(-6, 9)                                         # 0.015625 .. 256
+    text = np.array(['%g' % m for m in series], dtype=object)
+    pair = np.array(['%g/%g' % (m, m / 2) for m in series], dtype=object)
+
+    genome = np.sort(rng.integers(0, n_genomes, n_rows))
+    org = genome // genomes_per_org
+    # drugs are tested unevenly: some cases stay under min_entries
+    weight = 1.0 / (1 + np.arange(n_drugs)) ** 0.7
+    drug = rng.choice(n_drugs, n_rows, p=weight / weight.sum())
+    s_break = rng.integers(4, 8, (n_orgs, n_drugs))                          # index of the largest susceptible MIC
+    r_break = s_break + rng.integers(1, 3, (n_orgs, n_drugs))                # index of the smallest resistant MIC
+    resistant = rng.random(n_rows) < rng.random((n_orgs, n_drugs))[org, drug]
+    centre = np.where(resistant, r_break[org, drug] + 2, s_break[org, drug] - 2)
+    mic = np.clip(centre + np.rint(rng.normal(0, 1.6, n_rows)).astype(np.int64), 0, series.size - 1)
+    sir = np.where(mic <= s_break[org, drug], 0, np.where(mic >= r_break[org, drug], 1, 2))
+    sir = np.where(rng.random(n_rows) < 0.01, rng.integers(0, 3, n_rows), sir)      # a few calls disagree
+    sign = np.where(mic == 0, 3, np.where(mic == series.size - 1, 4, rng.choice(3, n_rows, p=[0.8, 0.15, 0.05])))
+    signs = np.array([np.nan, '=', '==', '<=', '>'], dtype=object)
+    prefix = np.array(['', '', '', '<=', '>'], dtype=object)
+    value = np.where(is_combo[drug], pair[mic], text[mic]).astype(object)
+    measurement = (prefix[sign] + value).astype(object)
+
+    kind = rng.choice(3, n_rows, p=[0.8, 0.1, 0.1])                          # a MIC, a disk diffusion, a phenotype alone
+    nothing = np.full(n_rows, np.nan, dtype=object)
+    by_kind = lambda mic_rows, disk_rows: np.where(kind == 0, mic_rows, np.where(kind == 1, disk_rows, nothing))   # noqa: E731
+    disk = np.array(['%d' % d for d in range(6, 40)], dtype=object)[rng.integers(0, 34, n_rows)]
+    value, measurement = by_kind(value, disk), by_kind(measurement, disk)
+    sign_col = by_kind(signs[sign], nothing)
+    unit = np.array(['mg/L', 'mm', np.nan], dtype=object)[kind]
+    methods = np.array(['broth_microdilution', 'etest', 'vitek_2', 'agar_dilution', 'sensititre', 'computational prediction'],
+                       dtype=object)
+    method = by_kind(methods[rng.choice(6, n_rows, p=[0.5, 0.15, 0.15, 0.1, 0.05, 0.05])],
+                     np.full(n_rows, 'disk_diffusion', dtype=object))
+    stnd_weight = rng.dirichlet([4, 2, 0.5, 1], n_orgs)
+    stnd = np.array(['clsi', 'eucast', 'missing', np.nan], dtype=object)[
+        (rng.random(n_rows)[:, None] > np.cumsum(stnd_weight, axis=1)[org]).sum(axis=1).clip(0, 3)]
+    for col in (value, measurement, sign_col, unit, method, stnd):           # one null object, whatever np.where made
+        col[pd.isnull(col)] = np.nan
+    df = pd.DataFrame({
+        'genome_id': gids[genome], 'genome_name': np.array(orgs, dtype=object)[org], 'taxon_id': 1000 + org, 'antibiotic': drugs[drug],
+        'resistant_phenotype': np.array(['susceptible', 'resistant', 'intermediate'], dtype=object)[sir], 'measurement': measurement,
+        'measurement_sign': sign_col, 'measurement_value': value, 'measurement_unit': unit, 'laboratory_typing_method': method,
+        'laboratory_typing_method_version': nothing, 'laboratory_typing_platform': nothing, 'vendor': nothing,
+        'testing_standard': stnd, 'testing_standard_year': np.where(pd.isnull(stnd), np.nan, 2015.0).astype(np.float64),
+        'computational_method': nothing, 'computational_method_version': nothing,
+        'source': np.full(n_rows, 'synthetic', dtype=object)}, columns=list(PATRIC_AMR_COLUMNS))
+    return org_to_gids, df
