@@ -1016,6 +1016,50 @@ int pgx_mic_infer_dev(pgx_ctx *ctx, const uint32_t *d_class_begin, uint32_t n_ca
                       const uint8_t *d_combo, const uint8_t *d_kind, const int32_t *d_token, const double *d_value, uint64_t n,
                       int32_t *d_out, void *stream);
 
+/* Gene content of tree nodes: the device step of get_node_gene_content (reference weboflife.py:16-35, one gene per call) for
+ * every gene of a table at once. The table is the presence bitmap of "K3" above with a species where it says genome: species
+ * s owns pgx_bitmap_stride_words(n_genes) words, gene g is bit g & 63 of word g >> 6.
+ *   leaf_species[n_nodes]   a species index >= 0: the node is MAPPED, and a leaf even where it has children, which are not
+ *                           consulted; -1: unmapped. Two nodes may map to one species; a species may be mapped by none.
+ *   child_off[n_nodes + 1], child[]   the children of node v are child[child_off[v] .. child_off[v + 1])
+ *   order[n_nodes], level_off[n_levels + 1]   every node once, grouped by height: order[level_off[h] .. level_off[h + 1]) are
+ *                           the nodes of height h. Height 0 holds the mapped nodes and the childless unmapped ones; any other
+ *                           node has height 1 + the largest height among its children.
+ *   out_counts[n_nodes][pgx_tree_content_stride(n_genes)]   (the stride is n_genes rounded up to a multiple of 4, so that rows
+ *                           are 16-byte aligned; pad entries are zero.) For a mapped node v, out_counts[v][g] is the bit
+ *                           (leaf_species[v], g); for a childless unmapped node 0; for any other node the sum of its
+ *                           children's entries.
+ *   out_totals[n_nodes]     may be NULL. 1 for a mapped node, 0 for a childless unmapped one, else the sum over the children.
+ * out_counts[v][g] / out_totals[v] is the reference's value for node v and gene g (0 / 0 where it gives nan).
+ * One launch per height on one stream, no atomics, integer sums in the children's order: the same input gives the same bytes
+ * on every call. n_nodes x stride past 2^31 entries and more than 2^31 edges fail with PGX_ERR_INVALID, as do level offsets
+ * that decrease or do not run from 0 to n_nodes; n_nodes = 0 does nothing.
+ *   pgx_tree_content      HOST pointers; the table as COO records (row_of_record = the gene, species_of_record), built on the
+ *                         device as for pgx_row_counts, duplicates reported through out_duplicates (may be NULL; the bitmap
+ *                         holds a bit once, so a table with duplicates is not the 0/1 table the caller meant). The device
+ *                         buffers stay in the context between calls. The tree is checked before anything is launched or
+ *                         written, PGX_ERR_INVALID otherwise: offsets that decrease or do not start at 0; a child that is no
+ *                         node; a node missing from or twice in `order`; a leaf_species below -1 or not below n_species; a
+ *                         mapped node above height 0, or an unmapped node with children at height 0; a child of an unmapped
+ *                         node that does not lie at a strictly lower height; a node that is a child of two nodes.
+ *   pgx_tree_content_dev  the caller's DEVICE pointers (d_bits 8-byte, d_out_counts 16-byte, the others 4-byte aligned) and
+ *                         workspace (pgx_tree_content_workspace_bytes(), 16-byte aligned; 0 for sizes that are refused; the
+ *                         kernels keep nothing there today). level_off alone is HOST memory: it sizes the launches. Plain
+ *                         launches on `stream`, which is not synchronised; inputs are not written, nothing outside the two
+ *                         outputs is. The tree is not checked: an id that is no node or no species is skipped and offsets
+ *                         are clamped to n_edges, so nothing outside the caller's buffers is read, the result for a broken
+ *                         tree being unspecified. */
+uint32_t pgx_tree_content_stride(uint32_t n_genes);
+size_t pgx_tree_content_workspace_bytes(uint32_t n_nodes, uint32_t n_genes, uint64_t n_edges);
+int pgx_tree_content(pgx_ctx *ctx, const int32_t *row_of_record, const int32_t *species_of_record, uint64_t n_records,
+                     uint32_t n_genes, uint32_t n_species, const int32_t *leaf_species, const uint32_t *child_off,
+                     const uint32_t *child, uint32_t n_nodes, const uint32_t *order, const uint32_t *level_off, uint32_t n_levels,
+                     uint32_t *out_counts, uint32_t *out_totals, uint64_t *out_duplicates);
+int pgx_tree_content_dev(pgx_ctx *ctx, const uint64_t *d_bits, uint32_t n_genes, uint32_t n_species,
+                         const int32_t *d_leaf_species, const uint32_t *d_child_off, const uint32_t *d_child, uint32_t n_nodes,
+                         uint64_t n_edges, const uint32_t *d_order, const uint32_t *level_off, uint32_t n_levels,
+                         uint32_t *d_out_counts, uint32_t *d_out_totals, void *d_workspace, size_t workspace_bytes, void *stream);
+
 /* feature names (pangenome.py:1944-1969) as fixed-width zero-padded ASCII records (numpy 'S<width>'):
  * <prefix><cluster>[<variant><member>]; variant NULL = gene names */
 int pgx_format_labels(const char *prefix, const char *variant, const int32_t *cluster, const int32_t *member,

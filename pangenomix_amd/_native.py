@@ -227,7 +227,13 @@ SIGNATURES = {
                                 _P, _P, C.c_uint64, _P]),
     'pgx_mic_infer_dev': (C.c_int, [_P, _P, C.c_uint32, _P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, _P, _P, _P,
                                     _P, _P, _P, C.c_uint64, _P, _P]),
-    'pgx_genome_sets_diff': (C.c_int, [_P, _P, _P, C.c_uint64, _P, _P, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P]),
+    'pgx_tree_content_stride': (C.c_uint32, [C.c_uint32]),
+    'pgx_tree_content_workspace_bytes': (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_uint64]),
+    'pgx_tree_content': (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _P,
+                                   _P, C.POINTER(C.c_uint64)]),
+    'pgx_tree_content_dev': (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_uint32, C.c_uint64, _P, _P, C.c_uint32, _P,
+                                       _P, _P, C.c_size_t, _P]),
+    'pgx_genome_sets_diff':(C.c_int, [_P, _P, _P, C.c_uint64, _P, _P, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P]),
     'pgx_genome_sets_diff_dev': (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P]),
     'pgx_cluster_greedy': (C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(ClusterParams), _P, _P, _P, _P,
                                      C.POINTER(C.c_uint32), C.POINTER(ClusterStats)]),
@@ -1223,6 +1229,54 @@ class Context(object):
         check(lib().pgx_mic_infer_dev(self._h, d_class_begin, int(n_cases), d_sir, d_role, d_fl_begin, d_tk_begin, int(n_entries),
                                       d_fvals, int(n_fvals), d_tvals, int(n_tvals), d_case, d_sign, d_combo, d_kind, d_token,
                                       d_value, int(n), d_out, stream))
+
+    # -- the gene content of every node of a tree (weboflife.get_node_gene_content_table) ---------------------------------------
+    def tree_content(self, rows, species, n_genes, n_species, leaf_species, child_off, child, order, level_off,
+                     return_totals=False, counts=None):
+        """(counts uint32 [n_nodes, tree_content_stride(n_genes)], duplicates), with return_totals (counts, totals uint32
+        [n_nodes], duplicates): how many of the mapped nodes at or below each node carry each gene, and how many mapped nodes
+        there are, for the 0/1 table whose ones are the records (rows[k], species[k]) and the tree pgx.h describes under
+        pgx_tree_content. Pad entries of counts are zero. counts: a C-contiguous uint32 array of that shape to write into
+        (a caller that asks chunk after chunk keeps one buffer, whose pages are then faulted in once)."""
+        rows, species = _coo_args(rows, species)
+        leaf_species = np.ascontiguousarray(leaf_species, dtype=np.int32)
+        child_off, child, order, level_off = (np.ascontiguousarray(a, dtype=np.uint32) for a in (child_off, child, order, level_off))
+        n_nodes = leaf_species.size
+        if leaf_species.ndim != 1 or child_off.shape != (n_nodes + 1,) or order.shape != (n_nodes,) or child.ndim != 1 \
+                or level_off.ndim != 1 or level_off.size < 1:
+            raise ValueError('leaf_species and order must hold n_nodes, child_off n_nodes + 1 and level_off n_levels + 1 entries')
+        if int(child_off[-1]) > child.size:
+            raise ValueError('child_off runs past the end of child')
+        shape = (n_nodes, self.tree_content_stride(n_genes))
+        if counts is None:
+            counts = np.zeros(shape, dtype=np.uint32)
+        elif not (isinstance(counts, np.ndarray) and counts.dtype == np.uint32 and counts.shape == shape and counts.flags.c_contiguous
+                  and counts.flags.writeable):
+            raise ValueError('counts must be a writeable C-contiguous uint32 array of shape %r' % (shape,))
+        totals = np.zeros(n_nodes, dtype=np.uint32) if return_totals else None
+        dup = C.c_uint64(0)
+        check(lib().pgx_tree_content(self._h, _ptr(rows), _ptr(species), rows.size, int(n_genes), int(n_species), _ptr(leaf_species),
+                                     _ptr(child_off), _ptr(child), n_nodes, _ptr(order), _ptr(level_off), level_off.size - 1,
+                                     _ptr(counts), _ptr(totals), C.byref(dup)))
+        return (counts, totals, int(dup.value)) if return_totals else (counts, int(dup.value))
+
+    @staticmethod
+    def tree_content_stride(n_genes):
+        return int(lib().pgx_tree_content_stride(int(n_genes)))
+
+    def tree_content_workspace_bytes(self, n_nodes, n_genes, n_edges):
+        return int(lib().pgx_tree_content_workspace_bytes(int(n_nodes), int(n_genes), int(n_edges)))
+
+    def tree_content_dev(self, d_bits, n_genes, n_species, d_leaf_species, d_child_off, d_child, n_nodes, n_edges, d_order,
+                         level_off, d_out_counts, d_out_totals, d_ws, ws_bytes, stream=0):
+        """The same on device memory (raw device addresses, None for no totals); level_off alone is a host array: it sizes the
+        launches. Only enqueues on `stream`, see pgx.h."""
+        level_off = np.ascontiguousarray(level_off, dtype=np.uint32)
+        if level_off.ndim != 1 or level_off.size < 1:
+            raise ValueError('level_off must hold n_levels + 1 entries')
+        check(lib().pgx_tree_content_dev(self._h, d_bits, int(n_genes), int(n_species), d_leaf_species, d_child_off, d_child,
+                                         int(n_nodes), int(n_edges), d_order, _ptr(level_off), level_off.size - 1, d_out_counts,
+                                         d_out_totals, d_ws, int(ws_bytes), stream))
 
     def pan_core(self, bits, n_genes, perms):
         perms = np.ascontiguousarray(perms, dtype=np.int32)

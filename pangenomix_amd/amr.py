@@ -54,7 +54,7 @@ _GraphError = _nx.NetworkXError if _nx is not None else AroGraphError
 
 class AroGraph(object):
     """A directed graph with the few methods this module needs, in the insertion order an nx.DiGraph keeps: `nodes` and
-    `edges` (lists), successors(), add_node(), add_edge(), remove_node(), `in` and len()."""
+    `edges` (lists), successors(), G[node], add_node(), add_edge(), remove_node(), `in` and len()."""
 
     def __init__(self):
         self._succ, self._pred = {}, {}
@@ -100,6 +100,10 @@ class AroGraph(object):
 
     def __len__(self):
         return len(self._succ)
+
+    def __getitem__(self, node):
+        """the successors of `node`, a mapping in insertion order as G[node] of an nx.DiGraph is (KeyError for no node)"""
+        return self._succ[node]
 
     def __iter__(self):
         return iter(self._succ)

@@ -79,6 +79,8 @@ enum DevSlot : int {        // pgx_ctx::arena, through DevBuf
     // mic.hip: pgx_tuple_group (the columns, the workspace, every result in one), then pgx_mic_infer (the case tables in
     // one, the row arrays in one, the codes)
     TG_SLOT_IN, TG_SLOT_WS, TG_SLOT_OUT, MI_SLOT_TABLES, MI_SLOT_ROWS, MI_SLOT_OUT,
+    // tree.hip: the species' table, the tree arrays in one, counts and totals in one
+    TR_SLOT_BITS, TR_SLOT_ROWS, TR_SLOT_SPECIES, TR_SLOT_CNT, TR_SLOT_IN, TR_SLOT_OUT,
     DEV_SLOT_COUNT
 };
 enum HostSlot : int {       // pgx_ctx::host_scratch, through HostVec

@@ -8,6 +8,7 @@ a 5 % tier substitutes 15-25 % (straddles the 0.8 threshold), and 1 % of the rec
 <= 10 residues long (exercises cd-hit's discard length).
 """
 
+import collections
 import os
 import sys
 
@@ -332,3 +333,57 @@ def patric_amr_table(n_rows=1000000, n_orgs=8, genomes_per_org=2000, n_drugs=40,
         'computational_method': nothing, 'computational_method_version': nothing,
         'source': np.full(n_rows, 'synthetic', dtype=object)}, columns=list(PATRIC_AMR_COLUMNS))
     return org_to_gids, df
+
+
+def phylogeny(n_species, seed, n_genes=100, max_children=4, mapped_internal=0, unmapped_leaves=0, unused_species=0):
+    """(G, root, mrca_to_species, df_genes_pa) for weboflife: a random rooted tree over n_species species as a
+    weboflife.PhyloGraph with branch lengths in the edge attribute 'len', and a matching gene x species
+    LightSparseDataFrame of ones. The tree is joined from the leaves up: two random subtrees at a time, three to
+    max_children in three joins out of ten (polytomies), so its height grows like the logarithm of n_species and a little
+    faster. Leaf 'L<i>' maps to species 'S<i>'; mapped_internal internal nodes (never the root) are mapped as well, each to
+    the species of a random leaf, so that two nodes share it; unmapped_leaves childless nodes 'U<i>' hang below random
+    internal nodes and map to nothing; unused_species further columns 'X<i>' are mapped by no node. A gene's frequency is
+    drawn from a U-shaped distribution (most genes rare, some in nearly every species)."""
+    import scipy.sparse as sp
+    from . import sparse_utils, weboflife
+    rng = np.random.default_rng(seed)
+    pool = ['L%d' % i for i in range(n_species)]
+    joins = []                                                                  # (parent, children), leaves first
+    while len(pool) > 1:
+        k = 2 if rng.random() < 0.7 or max_children < 3 else int(rng.integers(3, max_children + 1))
+        children = []
+        for _ in range(min(k, len(pool))):
+            at = int(rng.integers(0, len(pool)))
+            pool[at], pool[-1] = pool[-1], pool[at]
+            children.append(pool.pop())
+        parent = 'N%d' % len(joins)
+        joins.append((parent, children))
+        pool.append(parent)
+    root = pool[0]
+    extra = collections.defaultdict(list)
+    if joins:
+        for i, at in enumerate(rng.integers(0, len(joins), unmapped_leaves).tolist()):
+            extra[joins[at][0]].append('U%d' % i)
+    G = weboflife.PhyloGraph()
+    G.add_node(root)
+    for parent, children in reversed(joins):                                    # from the root down
+        for child in children + extra[parent]:
+            G.add_edge(parent, child, len=round(float(rng.uniform(0.01, 1.0)), 6))
+    mrca_to_species = {'L%d' % i: 'S%d' % i for i in range(n_species)}
+    inner = [parent for parent, _ in joins[:-1]]
+    for at in rng.permutation(len(inner))[:mapped_internal].tolist():
+        mrca_to_species[inner[at]] = 'S%d' % int(rng.integers(0, n_species))
+    n_columns = n_species + unused_species
+    frequency = rng.beta(0.25, 0.9, n_genes)
+    rows, cols = [], []
+    for lo in range(0, n_genes, 1024):                                          # (in slabs: the dense draw is the large part)
+        hit = rng.random((min(1024, n_genes - lo), n_columns), dtype=np.float32) < frequency[lo:lo + 1024, None]
+        r, c = np.nonzero(hit)
+        rows.append((r + lo).astype(np.int32))
+        cols.append(c.astype(np.int32))
+    rows = np.concatenate(rows) if rows else np.zeros(0, np.int32)
+    cols = np.concatenate(cols) if cols else np.zeros(0, np.int32)
+    data = sp.coo_matrix((np.ones(rows.size, dtype=np.int8), (rows, cols)), shape=(n_genes, n_columns))
+    index = np.array(['G%d' % g for g in range(n_genes)], dtype=object)
+    columns = np.array(['S%d' % s for s in range(n_species)] + ['X%d' % s for s in range(unused_species)], dtype=object)
+    return G, root, mrca_to_species, sparse_utils.LightSparseDataFrame(index, columns, data)
