@@ -54,6 +54,7 @@
 #include <vector>
 
 #include "cluster_layout.h"
+#include "cluster_resolve.h"
 #include "cluster_tables.h"
 #include "pgx_internal.h"
 
@@ -79,7 +80,7 @@ constexpr int kMaxBand = 64;
 
 __constant__ int8_t kBlosum62_dev[kNAA1 * kNAA1] = PGXC_BLOSUM62_FLAT;
 
-enum : uint32_t { F_DIAG_PASS = 1, F_BAND_OK = 2, F_ACCEPT = 4, F_TOO_BIG = 8, F_EVAL = 16, F_ALIGNED = 32 };
+// (Pair and its F_* flags, the ST_* member states, kNoBest and Chunks: cluster_resolve.h)
 // bits of a window's error word (counter C_ERR). In the record-sharded mode the word travels with every exchange of
 // the best keys and is OR-ed over the processes, so that every process sees the same word at the same point of the
 // window loop and all of them leave together.
@@ -89,16 +90,6 @@ enum : uint32_t { E_TOUCHED = 1,    // an append round set more entries aside th
                   E_BAND = 8,       // a pair that passed the diagonal test has a band wider than kMaxBand
                   E_PAIRS = 16,     // the window's candidate pair buffer overflowed
                   E_WORDMULT = 32 };// a word occurs more than 65535 times in one (giant, degenerate) sequence
-
-struct Pair {           // one (query, representative) candidate
-    uint32_t q;         // sorted sequence index of the query
-    uint32_t r;         // phase A: representative index; phase B: sorted sequence index
-    uint32_t cnt;       // short-word count
-    uint32_t minc;      // smallest shared word code (candidate order key)
-    int32_t best_sum, band_left, band_center, band_right;
-    int32_t iden;
-    uint32_t flags;
-};
 
 // Which pair records a diag / align launch works on: the device-side range
 // [*d_begin, min(*d_end, cap)) or an explicit list; optionally only pairs whose candidate (a
@@ -829,7 +820,6 @@ constexpr int kFHNt = 2048;        // ... nucleotides: one shared word makes a c
 constexpr uint32_t kFProbe = 24;   // probes before the exact table counts as full
 constexpr uint32_t kEmpty = 0xFFFFFFFFu;
 constexpr int kFWork = 32;         // residue-class work list per wave
-constexpr unsigned long long kNoBest = ~0ull;
 
 struct FilterArgs {
     const IndexLine *lines;
@@ -1498,8 +1488,6 @@ __global__ __launch_bounds__(256) void list_open_kernel(const unsigned long long
 // threshold (on both strands), no earlier open member can be its candidate: u is a new
 // representative for certain -- appended to the window's list of new representatives and made final.
 // Typically that is the first member of every family that appears in the window.
-constexpr uint32_t kMaxChunks = 32;
-struct Chunks { uint32_t n; uint32_t begin[kMaxChunks + 1]; };   // member ql belongs to chunk c: begin[c] <= ql < begin[c+1]
 __device__ __forceinline__ uint32_t chunk_of(const Chunks &C, uint32_t ql) {
     uint32_t c = 0;
     for (uint32_t t = 1; t < C.n; ++t) c += ql >= C.begin[t];
@@ -2362,11 +2350,27 @@ __global__ __launch_bounds__(256) void align_kernel(DevSeqs S, const uint32_t *_
 // ========================================================================================
 // host side: one call = upload, word lists, windows, in-order resolution, download
 // ========================================================================================
+// The driver is cluster_greedy_impl: a prologue, then a loop over the windows, each a sequence of phases. The
+// phases are functions over named state:
+//   ClusterCall    what the prologue fixes and what lives for the whole call: parameters, geometry, the workspace and
+//                  host buffers, the clustering so far (rep_seq, cluster_of, ...), the statistics
+//   WindowSet      sets[2]: what a window IN FLIGHT owns -- its stream, counters, best keys, member flags, pair
+//                  records, diagonal scratch, the pinned buffers its close publishes into, its two events.
+//                  Consecutive windows take the sets alternately (`overlap`), so window w + 1 can start while the
+//                  tail of window w still runs
+//   Window         what one iteration computes before it enqueues anything (members, slots, chunks, aligner slot,
+//                  the base FilterArgs) and the little it updates while it runs
+//   PendingWindow  a closed window whose host bookkeeping has not run yet
+// and run in this order:
+//   check_params, order_by_length (seq_len, histogram, host sort if the device cannot), prepare_input (run tables,
+//   thresholds, geometry, allocations, device sort, layout, encode / revcomp / pack), build_word_lists, plan_windows;
+//   per window: open_window, phase_a, discovery_rounds, resolve_blocks (enqueue_block, then walk_block of
+//   cluster_resolve.h alternating with follow_up_round, then retire_block), adapt_chunks, close_window;
+//   finish_window (the bookkeeping of window w) runs from begin_host_side of window w + 1, behind that window's first
+//   enqueues -- at once for nucleotides and PGX_TRACE=2; finish_call.
+// The host-only logic (window formation, threshold tables, the block walk, the counting passes) is in
+// cluster_resolve.h, where a plain program tests it.
 namespace {
-
-enum : uint8_t { ST_OPEN = 0, ST_MEMBER = 1, ST_REP = 2,
-                 ST_ABSENT = 3,    // memory-chunked rule: placed by an earlier chunk's sweep, not a member of this window any more
-                 ST_NONE = 4 };    // ... a sweep found no representative for it: it stays in the game
 
 #define LAUNCH_CHECK() PGX_HIP(hipGetLastError())
 
@@ -2417,6 +2421,10 @@ static int cluster_greedy_impl(pgx_ctx *ctx, const uint8_t *d_residues, const ui
 // The per-sequence host loops before and after the window loop (order, offsets, thresholds, outputs) run on a few
 // threads: with a million sequences they were a tenth of the call. fn(t, begin, end) for contiguous shares.
 // A few worker threads, started at the first large call and parked between regions.
+// No exception guard reaches a pool thread (the entry points' guarded() covers the calling thread only), so the bodies
+// handed to parallel_for must not throw: each of them only reads and writes arrays that exist before the region starts
+// -- no allocation, no container growth, no call that can fail. The std::function of a region is built on the calling
+// thread, inside the guard.
 namespace {
 class HostPool {
 public:
@@ -2496,8 +2504,10 @@ extern "C" int pgx_cluster_greedy_dev(pgx_ctx *ctx, const uint8_t *d_residues, c
                                       uint8_t *out_strand, uint32_t *out_n_clusters,
                                       pgx_cluster_stats *stats, void *stream_) {
     const auto t0 = std::chrono::steady_clock::now();
-    const int rc = cluster_greedy_impl(ctx, d_residues, d_offsets, n_in, total_in, P, out_cluster, out_member,
-                                       out_identity, out_strand, out_n_clusters, stats, stream_);
+    const int rc = guarded(__func__, [&] {
+        return cluster_greedy_impl(ctx, d_residues, d_offsets, n_in, total_in, P, out_cluster, out_member, out_identity,
+                                   out_strand, out_n_clusters, stats, stream_);
+    });
     if (std::getenv("PGX_TRACE"))
         fprintf(stderr, "[pgx] call total (incl. clean-up)    %8.2f ms\n",
                 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
@@ -2511,138 +2521,583 @@ extern "C" int pgx_cluster_greedy_dev(pgx_ctx *ctx, const uint8_t *d_residues, c
     return rc;
 }
 
-static int cluster_greedy_impl(pgx_ctx *ctx, const uint8_t *d_residues, const uint64_t *d_offsets,
-                               uint32_t n_in, uint64_t total_in, const pgx_cluster_params *P,
-                               int32_t *out_cluster, int32_t *out_member, float *out_identity,
-                               uint8_t *out_strand, uint32_t *out_n_clusters,
-                               pgx_cluster_stats *stats, void *stream_) {
-    PGX_REQUIRE(ctx && P, "NULL argument");
-    PGX_REQUIRE(n_in == 0 || (d_residues && d_offsets), "NULL sequence arrays");
-    PGX_REQUIRE(out_cluster && out_member && out_identity, "NULL output arrays");
-    PGX_REQUIRE(P->alphabet == 0 || P->alphabet == 1, "alphabet must be 0 (protein) or 1 (nucleotide)");
-    const bool nt = P->alphabet == 1;
-    const bool both = nt && P->both_strands != 0;
-    PGX_REQUIRE(P->word_len >= 2 && P->word_len <= (nt ? 11 : kMaxWordLen), "word_len must be 2..5 (protein) or 2..11 (nucleotide)");
-    PGX_REQUIRE(P->identity >= 0.4 && P->identity <= 1.0, "identity must be 0.4..1.0");
-    PGX_REQUIRE(P->band_width >= 1 && P->band_width <= kMaxBand, "band_width must be 1..64");
-    PGX_REQUIRE(P->min_length >= P->word_len - 1, "min_length must be at least word_len - 1");
-    PGX_REQUIRE(P->batch_size >= 0, "batch_size must not be negative");
-    PGX_REQUIRE(P->shard_count >= 0 && (P->shard_count == 0 ? P->shard_index == 0 : (P->shard_index >= 0 && P->shard_index < P->shard_count)),
-                "shard_index must be in [0, shard_count)");
-    // the exchange of the record-sharded mode: the caller's callback, or the context's own RCCL communicator
-    const bool native_exchange = !P->exchange && P->shard_count >= 1 && ctx->comm;
-    const bool exchanging = P->exchange || native_exchange;
-    PGX_REQUIRE(P->shard_count <= 1 || exchanging, "shard_count > 1 needs an exchange callback or a communicator (pgx_rccl_comm_create)");
-    PGX_REQUIRE(!native_exchange || (ctx->comm_world == P->shard_count && ctx->comm_rank == P->shard_index),
-                "shard_index / shard_count differ from the rank / size of the context's communicator");
-    PGX_REQUIRE(!P->exchange || (P->exchange_send && P->exchange_recv),
-                "the exchange callback needs exchange_send / exchange_recv (2 slots of PGX_EXCHANGE_WORDS uint64 per process, device memory)");
-    PGX_HIP(hipSetDevice(ctx->device_id));
-    hipStream_t st = (hipStream_t)stream_;
-    const auto t_call0 = std::chrono::steady_clock::now();
-    auto ms_since = [](std::chrono::steady_clock::time_point t) {
-        return 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count();
-    };
-    const bool trace_phases = std::getenv("PGX_TRACE") != nullptr;
-    double t_mark = 0.0;
-    auto phase = [&](const char *what) {   // PGX_TRACE: host wall time of the phases outside the window loop
-        if (!trace_phases) return;
-        const double now = ms_since(t_call0);
+// ========================================================================================
+// the driver's state
+// ========================================================================================
+namespace {
+
+// PGX_REQUIRE for the phases: the message names the function the check was cut from (error texts are interface)
+#define CL_REQUIRE_IN(fn, cond, msg)                                                       \
+    do {                                                                                   \
+        if (!(cond)) {                                                                     \
+            pgx_set_error("%s: %s", fn, msg);                                              \
+            return PGX_ERR_INVALID;                                                        \
+        }                                                                                  \
+    } while (0)
+#define CL_REQUIRE(cond, msg) CL_REQUIRE_IN("cluster_greedy_impl", cond, msg)
+
+constexpr uint32_t kHistWords = H_BINS + kDevSortMaxLen + 1;
+constexpr uint32_t kPrefix = 65536;  // initial capacity (records) of the host copy of the window's pairs
+constexpr uint32_t kFilterGrid = 4096u;
+constexpr uint32_t kAlignGrid = 1024;
+using Clock = std::chrono::steady_clock;
+inline double seconds_since(Clock::time_point t) { return std::chrono::duration<double>(Clock::now() - t).count(); }
+
+// What a window in flight owns. Consecutive windows overlap on two streams (proteins): the tail of window w -- the pass
+// over all members after its last block, that pass's diagonal tests and alignments, the close -- only READS the index,
+// and so does phase A of window w+1. Each window therefore has its own counters, best keys, member flags, pair records
+// and host copies (two sets, used alternately); window w+1 starts when the index of window w is final (`strike`: after
+// its last strike-out) and appends to the index only after window w's close (`post`).
+// A few hundred pairs per evaluation keep a 60-us dependent chain per alignment on the path otherwise.
+// (Record-sharded mode too: the exchange buffers have one slot per window in flight, and every process enqueues its
+// collectives in the same order because the host logic is the same function of replicated results.)
+struct WindowSet {
+    DevBuf counters_buf, best_buf, flags_buf, pairs_buf, gscratch_buf;   // the workspace slots behind the pointers below
+    hipStream_t st = nullptr;
+    uint32_t *dc = nullptr;                 // counters (C_*)
+    unsigned long long *d_best = nullptr;   // best key per member (this set's slot of the exchange buffer in the record-sharded mode)
+    uint8_t *d_done = nullptr, *d_inblk = nullptr, *d_hascand = nullptr, *d_accepted = nullptr;   // per member
+    Pair *pairsW = nullptr;                 // the window's candidate pairs
+    uint32_t *d_gs = nullptr;               // global scratch of the diag kernel (long sequences only)
+    // what the window's CLOSE publishes has its own host buffers
+    Pinned<Pair> hW;
+    Pinned<unsigned long long> h_best;
+    Pinned<uint32_t> h_ccnt;
+    hipEvent_t strike = nullptr, post = nullptr;   // (destroyed on every way out)
+    WindowSet(pgx_ctx *c, DevSlot counters, DevSlot best, DevSlot flags, DevSlot pairs, DevSlot gscratch, PinSlot w,
+              PinSlot b, PinSlot cnt)
+        : counters_buf(c, counters), best_buf(c, best), flags_buf(c, flags), pairs_buf(c, pairs), gscratch_buf(c, gscratch),
+          hW(c, w), h_best(c, b), h_ccnt(c, cnt) {}
+    WindowSet(const WindowSet &) = delete;
+    WindowSet &operator=(const WindowSet &) = delete;
+    ~WindowSet() {
+        if (strike) (void)hipEventDestroy(strike);
+        if (post) (void)hipEventDestroy(post);
+    }
+};
+
+// A closed window whose bookkeeping has not run: what finish_window needs of it.
+struct PendingWindow {
+    bool pending = false;
+    uint32_t b0 = 0, nb = 0, nW = 0;
+    bool sweep = false;
+    int set = 0;
+    uint64_t window_words = 0;
+    Pinned<Pair> *hW = nullptr;                 // that set's pinned buffers
+    Pinned<unsigned long long> *h_best = nullptr;
+    Pinned<uint32_t> *h_ccnt = nullptr;
+};
+
+// What is fixed once the prologue has run, and what lives for the whole call.
+struct ClusterCall {
+    // ---- the call ----
+    pgx_ctx *ctx;
+    const pgx_cluster_params *P;
+    hipStream_t st_main;
+    const uint8_t *d_residues = nullptr;
+    const uint64_t *d_offsets = nullptr;
+    uint32_t n_in = 0;
+    uint64_t total_in = 0;
+    int32_t *out_cluster = nullptr, *out_member = nullptr;
+    float *out_identity = nullptr;
+    uint8_t *out_strand = nullptr;
+    bool want_stats = false;
+    bool nt, both, overlap, exchanging, native_exchange, count_replicated;
+    uint32_t shard_index, shard_count;
+    bool trace, trace2;
+    unsigned nth = 1;   // host threads of the per-sequence loops
+    Clock::time_point t_call0, t_loop0;
+    double t_mark = 0.0, t_resolve = 0.0, t_close = 0.0;
+    // ---- the input's shape and the geometry derived from it ----
+    bool dev_sort = false, need_gscratch = false, chunking = false;
+    uint32_t n = 0, nv = 0, max_len = 0, n_runs = 0, mshift = 8, n_codes = 1, bm_words = 0;
+    uint32_t window_cap = 0, pair_cap_k = 0, packed_len = 0, diag_grid = 0, gs_stride = 0, gs_cells = 0, tag_stride = 1;
+    uint64_t total = 0, total_pk = 0, max_window_words = 0;
+    double thr_frac = 0.0;
+    const uint32_t *len_hist = nullptr;   // [L] = sequences of L letters that pass min_length
+    std::vector<uint32_t> host_hist;      // ... when the host sorted
+    uint64_t *run_off = nullptr;          // run tables (cluster_layout.h), in h_runs
+    uint32_t *run_pos = nullptr, *run_pk = nullptr;
+    std::vector<uint32_t> flush_at;       // cd-hit's memory-chunked rule (pgx.h): flush positions in the sorted list; a window never crosses one
+    DevSeqs DS{};
+    // ---- what the window loop changes ----
+    uint32_t pair_cap = 4u << 20;  // grows per window for nucleotides, whose word filter passes almost every pair
+    uint32_t block_cap = 0;
+    int pool_cur = 0;
+    uint64_t pool_cap = 0;
+    uint32_t epoch_idx = 0;      // append rounds of the index (line.epoch); 0 = never
+    uint32_t epoch_tag = 0;      // discovery rounds (first-open tags, 16 bits)
+    double cur_frac = 0.0;       // the chunk volume adapts, see adapt_chunks
+    uint64_t chunk_words = 0;
+    uint64_t pending_words = 0;  // words of the window whose bookkeeping is pending (its members count as representatives)
+    PendingWindow pending;
+    // ---- device workspace ----
+    DevBuf d_res, d_off, d_len, d_wcode, d_wmult, d_wcnt, d_aa1, d_aas, d_aan, d_lines, d_pool[2], d_idx, d_newbits, d_touched,
+        d_first, d_rcvis, d_visits, d_pairsK, d_blk_list, d_ulist, d_new_list, d_order, d_list, d_gather, d_pk, d_pkoff, d_thr,
+        d_hugewords, d_xsend, d_xrecv,
+        d_hist, d_sortcnt, d_tilesum, d_runs, d_in_len;   // the prologue's histogram, sort counters, run tables, input lengths
+    WindowSet sets[2];
+    unsigned long long *x_send = nullptr;         // the exchange buffers of the record-sharded mode
+    const unsigned long long *x_recv = nullptr;
+    // ---- host arrays (the per-sequence ones live in the context's scratch: no allocation, page faults or frees per call) ----
+    HostVec<uint32_t> h_hist, order, h_len, h_wcnt;
+    HostVec<uint64_t> h_off, h_runs;
+    HostVec<int32_t> h_thr;
+    HostVec<int32_t> cluster_of;   // sorted sequence index -> cluster
+    HostVec<int32_t> iden_of;      // identical residues against the representative, -1 = is one
+    HostVec<uint8_t> strand_of;
+    Pinned<Pair> hK, h_gather;
+    Pinned<unsigned long long> h_rcvis;
+    Pinned<uint32_t> h_cnt, h_blk, h_new, h_list, h_push;
+    Pinned<uint8_t> h_taken;   // per sorted sequence: placed by a sweep (the device reads it through the mapping)
+    std::vector<uint32_t> rep_seq;   // representative index -> sorted sequence index
+    std::vector<uint32_t> members;   // cluster -> members numbered so far
+    std::vector<uint8_t> status;     // per window member: ST_*
+    std::vector<unsigned long long> winner_key;  // strand<<63 | minc<<32 | sequence index of the winner
+    std::vector<uint32_t> order_k, rank_of, bucket_k, fill_k, flight;   // the block walk's
+    // ---- statistics ----
+    pgx_cluster_stats S{};
+    uint64_t gpu_pairs = 0, gpu_aligned = 0, gpu_aligned_bytes = 0, filter_walk_words = 0;  // actual device work (reserved stats slots)
+    uint64_t visits_rc = 0, n_rounds = 0, n_blocks = 0;
+    // test hook (tests/test_gpu_cluster_sharded.py): PGX_INJECT_ERROR="<rank>:<n>" makes that process report a pair
+    // buffer overflow with its n-th exchange, to check that every process then leaves at the same point
+    int inject_rank = -1;
+    uint64_t inject_at = 0, n_exchanges = 0;
+
+    ClusterCall(pgx_ctx *c, const pgx_cluster_params *p, hipStream_t stream)
+        : ctx(c), P(p), st_main(stream),
+          d_res(c, CL_SLOT_RES), d_off(c, CL_SLOT_OFF), d_len(c, CL_SLOT_LEN), d_wcode(c, CL_SLOT_WCODE), d_wmult(c, CL_SLOT_WMULT),
+          d_wcnt(c, CL_SLOT_WCNT), d_aa1(c, CL_SLOT_AA1), d_aas(c, CL_SLOT_AAS), d_aan(c, CL_SLOT_AAN), d_lines(c, CL_SLOT_LINES),
+          d_pool{{c, CL_SLOT_POOL0}, {c, CL_SLOT_POOL1}}, d_idx(c, CL_SLOT_IDX), d_newbits(c, CL_SLOT_NEWBITS),
+          d_touched(c, CL_SLOT_TOUCHED), d_first(c, CL_SLOT_FIRST), d_rcvis(c, CL_SLOT_RCVIS), d_visits(c, CL_SLOT_VISITS),
+          d_pairsK(c, CL_SLOT_PAIRS_K), d_blk_list(c, CL_SLOT_BLK_LIST), d_ulist(c, CL_SLOT_ULIST), d_new_list(c, CL_SLOT_NEW_LIST),
+          d_order(c, CL_SLOT_ORDER), d_list(c, CL_SLOT_LIST), d_gather(c, CL_SLOT_GATHER), d_pk(c, CL_SLOT_PK),
+          d_pkoff(c, CL_SLOT_PKOFF), d_thr(c, CL_SLOT_THR), d_hugewords(c, CL_SLOT_HUGEWORDS), d_xsend(c, CL_SLOT_XSEND),
+          d_xrecv(c, CL_SLOT_XRECV), d_hist(c, CL_SLOT_HIST), d_sortcnt(c, CL_SLOT_SORTCNT), d_tilesum(c, CL_SLOT_TILESUM),
+          d_runs(c, CL_SLOT_RUNS), d_in_len(c, CL_SLOT_IN_LEN),
+          sets{{c, CL_SLOT_COUNTERS, CL_SLOT_BEST_OWN, CL_SLOT_FLAGS, CL_SLOT_PAIRS_W, CL_SLOT_GSCRATCH, CL_PIN_W, CL_PIN_BEST, CL_PIN_CCNT},
+               {c, CL_SLOT_COUNTERS2, CL_SLOT_BEST2, CL_SLOT_FLAGS2, CL_SLOT_PAIRS_W2, CL_SLOT_GSCRATCH2, CL_PIN_W2, CL_PIN_BEST2, CL_PIN_CCNT2}},
+          hK(c, CL_PIN_K), h_gather(c, CL_PIN_GATHER), h_rcvis(c, CL_PIN_RCVIS), h_cnt(c, CL_PIN_CNT), h_blk(c, CL_PIN_BLK),
+          h_new(c, CL_PIN_NEW), h_list(c, CL_PIN_LIST), h_push(c, CL_PIN_PUSH), h_taken(c, CL_PIN_TAKEN) {
+        nt = P->alphabet == 1;
+        both = nt && P->both_strands != 0;
+        // the exchange of the record-sharded mode: the caller's callback, or the context's own RCCL communicator
+        native_exchange = !P->exchange && P->shard_count >= 1 && ctx->comm;
+        exchanging = P->exchange || native_exchange;
+        // record-sharded mode (see pgx.h): this process filters and aligns the window members ql % shard_count ==
+        // shard_index; the window's best keys live in the exchange buffer and are all-gathered after every evaluation
+        shard_count = P->shard_count > 0 ? (uint32_t)P->shard_count : 1u;
+        shard_index = P->shard_count > 0 ? (uint32_t)P->shard_index : 0u;
+        count_replicated = shard_index == 0;  // work every process repeats is counted by the first one only
+        overlap = !nt && !std::getenv("PGX_NO_OVERLAP");   // consecutive windows on two streams, see WindowSet
+        const char *tr = std::getenv("PGX_TRACE");
+        trace = tr != nullptr;
+        trace2 = trace && tr[0] == '2';
+        sets[0].st = st_main;
+        sets[1].st = ctx->stream2;
+        t_call0 = t_loop0 = Clock::now();
+    }
+    void phase(const char *what) {   // PGX_TRACE: host wall time of the phases outside the window loop
+        if (!trace) return;
+        const double now = 1e3 * seconds_since(t_call0);
         fprintf(stderr, "[pgx] %-28s %8.2f ms\n", what, now - t_mark);
         t_mark = now;
-    };
-    pgx_cluster_stats S{};
-    S.n_input = n_in;
-    if (out_n_clusters) *out_n_clusters = 0;
-    const unsigned nth = host_threads(n_in);
-    parallel_for(n_in, nth, [&](unsigned, size_t b, size_t e) {
-        for (size_t i = b; i < e; ++i) {
-            out_cluster[i] = -1; out_member[i] = -1; out_identity[i] = 0.f;
-            if (out_strand) out_strand[i] = 0;
-        }
-    });
-    if (n_in == 0) { if (stats) *stats = S; return PGX_OK; }
+    }
+    void give_stats(pgx_cluster_stats *stats) const { if (stats) *stats = S; }
+};
 
-    // ---- A.2 / A.3: letters -> indices, stable descending-length order ---------------------
-    // The GPU counts letters, orders the sequences and lays them out; the host sees the lengths as a histogram (one
-    // small copy, one synchronisation) and derives its O(longest length) bookkeeping from that. Its per-sequence arrays
-    // are filled behind the enqueued device work.
-    DevBuf d_res(ctx, CL_SLOT_RES), d_off(ctx, CL_SLOT_OFF), d_len(ctx, CL_SLOT_LEN), d_wcode(ctx, CL_SLOT_WCODE),
-        d_wmult(ctx, CL_SLOT_WMULT), d_wcnt(ctx, CL_SLOT_WCNT), d_aa1(ctx, CL_SLOT_AA1), d_aas(ctx, CL_SLOT_AAS),
-        d_aan(ctx, CL_SLOT_AAN), d_lines(ctx, CL_SLOT_LINES), d_pool[2] = {{ctx, CL_SLOT_POOL0}, {ctx, CL_SLOT_POOL1}},
-        d_idx(ctx, CL_SLOT_IDX), d_newbits(ctx, CL_SLOT_NEWBITS), d_touched(ctx, CL_SLOT_TOUCHED), d_first(ctx, CL_SLOT_FIRST),
-        d_best_own(ctx, CL_SLOT_BEST_OWN), d_rcvis(ctx, CL_SLOT_RCVIS), d_counters(ctx, CL_SLOT_COUNTERS),
-        d_visits(ctx, CL_SLOT_VISITS), d_pairsW(ctx, CL_SLOT_PAIRS_W), d_pairsK(ctx, CL_SLOT_PAIRS_K),
-        d_blk_list(ctx, CL_SLOT_BLK_LIST), d_ulist(ctx, CL_SLOT_ULIST), d_new_list(ctx, CL_SLOT_NEW_LIST),
-        d_flags(ctx, CL_SLOT_FLAGS), d_gscratch(ctx, CL_SLOT_GSCRATCH), d_order(ctx, CL_SLOT_ORDER), d_list(ctx, CL_SLOT_LIST),
-        d_gather(ctx, CL_SLOT_GATHER), d_pk(ctx, CL_SLOT_PK), d_pkoff(ctx, CL_SLOT_PKOFF),
-        // second set of a window's own state (see `overlap`)
-        d_counters2(ctx, CL_SLOT_COUNTERS2), d_best2(ctx, CL_SLOT_BEST2), d_flags2(ctx, CL_SLOT_FLAGS2),
-        d_pairsW2(ctx, CL_SLOT_PAIRS_W2), d_gscratch2(ctx, CL_SLOT_GSCRATCH2),
-        d_thr(ctx, CL_SLOT_THR), d_hugewords(ctx, CL_SLOT_HUGEWORDS), d_xsend(ctx, CL_SLOT_XSEND), d_xrecv(ctx, CL_SLOT_XRECV),
-        // the prologue's histogram, sort counters, run tables
-        d_hist(ctx, CL_SLOT_HIST), d_sortcnt(ctx, CL_SLOT_SORTCNT), d_tilesum(ctx, CL_SLOT_TILESUM), d_runs(ctx, CL_SLOT_RUNS);
-    uint32_t n_codes = 1;
-    for (int t = 0; t < P->word_len; ++t) n_codes *= nt ? 4u : (uint32_t)kNAA1;
+// What one iteration of the window loop computes before it enqueues anything, and the little it updates while it runs.
+struct Window {
+    uint32_t b0 = 0, nb = 0, ns = 0;   // first member, members, slots (+ one per reverse complement)
+    bool sweep = false;                // a window of a sweep: phase A only, nothing is appended
+    bool mark_absent = false;          // some members may have been placed by a sweep before
+    int set = 0;
+    uint32_t n_reps = 0;               // representatives at entry
+    uint64_t window_words = 0, blocks_before = 0;
+    int two_len = 0, a16_slot = 0;     // LDS slot per pair of the 16-lane aligner: sized for two sequences as long as the window's longest query
+    uint32_t *d_poolp = nullptr;       // the index's overflow pool as it is for this window
+    Chunks chunks;
+    FilterArgs FA{};
+    Clock::time_point t_sweep0;
+    // Can a pair of the evaluation at hand fall outside the 16-lane aligner's slots? Its band cannot when the band
+    // width is at most 32; its lengths can when the candidates are OLDER representatives (the pass over the whole
+    // index: any length) or when the window's own longest pair exceeds the largest slot. Every other evaluation
+    // pairs members of this window with each other -- two sequences no longer than the window's first, which is
+    // what the slot was sized for -- and does not launch the general aligner at all (an empty launch is ≈ 11 us of
+    // stream time, 105 of them per step on cfg-3s).
+    bool older_reps = false;
+    uint32_t n_listed = 0;             // discovery representatives the host has seen
+    uint32_t n_struck = 0;             // members struck out of the index so far (offsets into the pinned list)
+    bool strike_recorded = false;
+    uint32_t nW = 0;                   // pair records the close published (known here without overlap only)
+};
+
+// The fraction of the word threshold fraction that one discovery chunk's words may cover (PGX_CHUNK_FRAC).
+// (0.8 of the threshold fraction: unrelated members alone then share 17 % of their words with a chunk by chance,
+// against a threshold of 23 %. Measured, cfg-3s / cfg-4 / 300,000 unrelated random proteins: 0.4 -> 101 ms / 1.57 s /
+// 49 ms, 0.8 -> 94 ms / 1.3 s / 64 ms, 1.0 -> 93 ms / 1.26 s / 82 ms -- families fill far less of the code space than
+// their word count, so larger chunks mean fewer, larger windows; without families the test starts to fail.)
+double chunk_frac_default() {
+    static const double chunk_frac = std::getenv("PGX_CHUNK_FRAC") ? std::atof(std::getenv("PGX_CHUNK_FRAC")) : 0.8;
+    return chunk_frac;
+}
+
+// ========================================================================================
+// the window helpers
+// ========================================================================================
+
+// overflow pool of the index: sized before every window from the entries that exist and the most the
+// window can add (every array is re-allocated with twice the need: <= 8 words per entry in all)
+int ensure_pool(ClusterCall &C, uint64_t entries, hipStream_t on) {
+    const uint64_t need = 8 * entries + 4096;
+    if (need <= C.pool_cap) return PGX_OK;
+    if (need > 0xFFFFFFF0ull) { pgx_set_error("pgx_cluster_greedy: word index too large for 32-bit pool offsets"); return PGX_ERR_CAPACITY; }
+    const uint64_t want = std::min<uint64_t>(0xFFFFFFF0ull, need + need / 2);
+    DevBuf &nb_ = C.d_pool[C.pool_cur ^ 1];
+    PGX_HIP(nb_.alloc(want * 4));
+    if (C.pool_cap) PGX_HIP(hipMemcpyAsync(nb_.p, C.d_pool[C.pool_cur].p, C.pool_cap * 4, hipMemcpyDeviceToDevice, on));
+    C.pool_cur ^= 1;
+    C.pool_cap = want;
+    return PGX_OK;
+}
+
+uint32_t form_window(const ClusterCall &C, uint32_t b0, Chunks &chunks, uint32_t limit) {
+    return pgxc::form_window(C.h_len.data(), b0, limit, C.window_cap, C.chunking, C.chunk_words, chunks);
+}
+
+void account(ClusterCall &C, const Pair *pp, uint32_t cnt) {
+    for (uint32_t i = 0; i < cnt; ++i) {
+        ++C.gpu_pairs;
+        if (!pair_is_aligned(pp[i])) continue;
+        ++C.gpu_aligned;
+        C.gpu_aligned_bytes += C.h_len[pp[i].q] + C.h_len[pp[i].r];
+    }
+}
+
+void add_counts(pgx_cluster_stats &S, const PairCounts &c) {
+    S.filter_pairs += c.filter_pairs; S.aligned_pairs += c.aligned_pairs;
+    S.aligned_rep_len += c.aligned_rep_len; S.dp_cells += c.dp_cells;
+}
+
+void window_error(const ClusterCall &C, uint32_t e, uint32_t at) {   // (the word is the OR over all processes in the record-sharded mode)
+    pgx_set_error("pgx_cluster_greedy: capacity failure in the window at %u%s:%s%s%s%s%s%s", at,
+                  C.exchanging ? " (on this or another process)" : "",
+                  e & E_TOUCHED ? " append scratch list full;" : "", e & E_POOL ? " overflow pool of the word index full;" : "",
+                  e & E_TABLE ? " exact table of the filter overflowed;" : "",
+                  e & E_BAND ? " alignment band wider than 64 diagonals;" : "", e & E_PAIRS ? " candidate pair buffer overflow;" : "",
+                  e & E_WORDMULT ? " a word occurs more than 65535 times in one sequence;" : "");
+}
+
+int band_error() {
+    pgx_set_error("pgx_cluster_greedy: alignment band wider than %d diagonals", kMaxBand);
+    return PGX_ERR_CAPACITY;
+}
+
+// diag + align of a selection of pair records, enqueued on the window's stream
+int evaluate(ClusterCall &C, WindowSet &ws, Window &W, Pair *pairs, const PairSel &sel, unsigned long long *best_arr,
+             uint32_t grid_hint) {
+    const pgx_cluster_params *P = C.P;
+    const uint32_t dg = grid_hint ? std::min(C.diag_grid, grid_hint) : C.diag_grid;
+    const uint32_t ag = grid_hint ? std::min(kAlignGrid, (grid_hint + 15) / 16) : kAlignGrid;
+    const uint32_t len0 = C.h_len[W.b0];
+    {
+        ProfScope prof(C.ctx, "diag_kernel", ws.st);
+        // (LDS by the window's longest query: 512 positions give six waves per SIMD, 1024 four, 2048 two and a half)
+        auto kern = len0 > C.packed_len ? diag_kernel<64, unsigned long long>
+                    : (len0 <= kDiagLdsSmall ? diag_kernel<kDiagLdsSmall, uint32_t>
+                       : (len0 <= 2 * kDiagLdsSmall ? diag_kernel<2 * kDiagLdsSmall, uint32_t> : diag_kernel<kDiagLdsCap, uint32_t>));
+        kern<<<dg, 64, 0, ws.st>>>(C.DS, nullptr, pairs, sel, C.d_aa1.as<int32_t>(), C.d_aas.as<int32_t>(),
+                                   P->band_width, P->identity, ws.d_gs, C.gs_stride, C.gs_cells, ws.dc + C_WIDE, ws.dc + C_ERR);
+    }
+    LAUNCH_CHECK();
+    {
+        ProfScope prof(C.ctx, "align_kernel", ws.st);
+        const int a16_slot = W.a16_slot, two_len = W.two_len;
+        auto kern = a16_slot == 1024 ? align16_kernel<1024> : (a16_slot == 1536 ? align16_kernel<1536> : (a16_slot == 2048 ? align16_kernel<2048>
+                    : (a16_slot == 3072 ? align16_kernel<3072> : align16_kernel<kA16MaxSlot>)));
+        kern<<<ag, 256, 0, ws.st>>>(C.DS, nullptr, pairs, sel, C.d_aa1.as<int32_t>(), P->identity, W.b0, best_arr, 0u, ws.dc + C_WIDE, 0u);
+        // a window whose longest query does not fit the 4 KB slots twice over: the pairs left get 8 KB slots (the
+        // general aligner computes a cell per lane every OTHER step, one pair per wave: 1.6 ms for the first
+        // window of cfg-3s, whose longest sequences are 2,101 residues)
+        const bool big_pass = a16_slot == kA16MaxSlot && two_len > kA16MaxSlot - 96;
+        const bool may_be_wide = W.older_reps || two_len > a16_slot - 96 || P->band_width > 32;
+        if (big_pass)
+            align16_kernel<kA16BigSlot><<<ag, 256, 0, ws.st>>>(C.DS, nullptr, pairs, sel, C.d_aa1.as<int32_t>(), P->identity, W.b0, best_arr,
+                                                               0u, ws.dc + C_WIDE, 1u);
+        if (may_be_wide)
+            align_kernel<<<grid_hint ? std::min(kAlignGrid, (grid_hint + 3) / 4) : kAlignGrid, 256, 0, ws.st>>>(
+                C.DS, nullptr, pairs, sel, C.d_aa1.as<int32_t>(), P->identity, W.b0, best_arr, 0u, 1, (big_pass ? kA16BigSlot : a16_slot) - 96, ws.dc + C_WIDE);
+    }
+    LAUNCH_CHECK();
+    return PGX_OK;
+}
+
+// record-sharded mode: every process learns every member's best key (one all-gather per evaluation,
+// enqueued on the stream by the caller's collective library; no host synchronisation)
+int exchange_best(ClusterCall &C, WindowSet &ws, Window &W) {
+    if (!C.exchanging) return PGX_OK;
+    const pgx_cluster_params *P = C.P;
+    ++C.n_exchanges;
+    exchange_prepare_kernel<<<1, 1, 0, ws.st>>>(ws.dc, C.pair_cap, ws.d_best,
+                                                C.inject_rank == (int)C.shard_index && C.inject_at == C.n_exchanges ? (uint32_t)E_PAIRS : 0u);
+    if (C.native_exchange) {
+        const int rc = pgx_rccl_all_gather_u64(C.ctx, C.x_send + (size_t)W.set * PGX_EXCHANGE_WORDS,
+                                               const_cast<unsigned long long *>(C.x_recv) + (size_t)W.set * C.shard_count * PGX_EXCHANGE_WORDS,
+                                               PGX_EXCHANGE_WORDS, ws.st);
+        if (rc) return rc;
+    } else if (P->exchange(P->exchange_user, (void *)ws.st, W.set) != 0) {
+        pgx_set_error("pgx_cluster_greedy: the exchange callback failed in the window at %u", W.b0);
+        return PGX_ERR_INTERNAL;
+    }
+    min_rows_kernel<<<(W.nb + 255) / 256, 256, 0, ws.st>>>(
+        C.x_recv + (size_t)W.set * C.shard_count * PGX_EXCHANGE_WORDS,
+        C.shard_count, PGX_EXCHANGE_WORDS, W.nb, ws.d_best, ws.dc + C_ERR);
+    LAUNCH_CHECK();
+    return PGX_OK;
+}
+
+// the window's pairs found since the last round_begin: evaluated, winners folded into best[]
+int evaluate_round(ClusterCall &C, WindowSet &ws, Window &W) {
+    const PairSel sel{ws.dc + C_EVAL0, ws.dc + C_NW, C.pair_cap, nullptr, 0, nullptr, nullptr, nullptr, W.b0, 0, 0};
+    int rc = evaluate(C, ws, W, ws.pairsW, sel, ws.d_best, 0);
+    if (rc) return rc;
+    return exchange_best(C, ws, W);
+}
+
+// append list[*lo, *hi) to the index as round `epoch_idx` (the bit map of touched codes is the round's)
+int index_append(ClusterCall &C, WindowSet &ws, Window &W, const uint32_t *list, const uint32_t *d_lo, const uint32_t *d_hi) {
+    ++C.epoch_idx;
+    uint32_t *const map = C.d_newbits.as<uint32_t>() + (size_t)(C.epoch_idx & 1u) * C.bm_words;   // (clear: index_place_kernel of the round before)
+    uint32_t *const next_map = C.d_newbits.as<uint32_t>() + (size_t)((C.epoch_idx + 1u) & 1u) * C.bm_words;
+    ProfScope prof(C.ctx, "index_append", ws.st);
+    index_append_kernel<<<512, 256, 0, ws.st>>>(C.DS, list, d_lo, d_hi, C.d_lines.as<IndexLine>(), C.epoch_idx,
+                                                map, W.b0, W.nb, C.d_touched.as<Deferred>(),
+                                                ws.dc + C_TOUCH, (uint32_t)C.max_window_words, ws.dc + C_ERR);
+    index_grow_kernel<<<256, 256, 0, ws.st>>>(C.d_lines.as<IndexLine>(), W.d_poolp, C.d_idx.as<uint32_t>(),
+                                              (uint32_t)C.pool_cap, C.d_touched.as<Deferred>(), ws.dc + C_TOUCH,
+                                              (uint32_t)C.max_window_words, ws.dc + C_ERR);
+    index_place_kernel<<<256, 256, 0, ws.st>>>(C.d_lines.as<IndexLine>(), W.d_poolp, C.d_touched.as<Deferred>(),
+                                               ws.dc + C_TOUCH, (uint32_t)C.max_window_words, reinterpret_cast<uint4 *>(next_map),
+                                               C.bm_words / 4);
+    LAUNCH_CHECK();
+    return PGX_OK;
+}
+
+// every window member against the entries round `epoch_idx` added (the representatives list[*lo, *hi))
+int filter_new_and_evaluate(ClusterCall &C, WindowSet &ws, Window &W, const uint32_t *d_lo, const uint32_t *d_hi) {
+    FilterArgs F = W.FA;
+    F.epoch = C.epoch_idx; F.d_round_lo = d_lo; F.d_round_hi = d_hi;
+    F.newbits = C.d_newbits.as<uint32_t>() + (size_t)(C.epoch_idx & 1u) * C.bm_words;
+    {
+        ProfScope prof(C.ctx, "filter_kernel<new>", ws.st);
+        auto kern = C.nt ? filter_kernel<true, true> : filter_kernel<false, true>;
+        kern<<<std::min(kFilterGrid, (W.ns + 3) / 4), 256, 0, ws.st>>>(C.DS, F);
+    }
+    LAUNCH_CHECK();
+    C.filter_walk_words += W.window_words * (C.both ? 2 : 1) / C.shard_count;
+    return evaluate_round(C, ws, W);
+}
+
+// ---- the bookkeeping of a closed window --------------------------------------------------
+// What the close published is looked at by the window's bookkeeping, which waits for it first: with
+// overlapping windows that is when the next window's first kernels have been enqueued, without right at the close.
+int wait_closed(ClusterCall &C, PendingWindow &pw) {
+    WindowSet &ws = C.sets[pw.set];
+    if (C.overlap) {
+        const auto t0 = Clock::now();
+        hipError_t e;
+        while ((e = hipEventQuery(ws.post)) == hipErrorNotReady) {
+        }
+        g_wait_s += seconds_since(t0);
+        PGX_HIP(e);
+    } else {
+        PGX_HIP(spin_sync(ws.st));
+    }
+    pw.nW = pw.h_ccnt->p[C_NW];
+    if (pw.h_ccnt->p[C_ERR]) { window_error(C, pw.h_ccnt->p[C_ERR], pw.b0); return PGX_ERR_CAPACITY; }
+    if (pw.nW > C.pair_cap) {
+        pgx_set_error("pgx_cluster_greedy: candidate pair buffer overflow (%u > %u) in the window at %u", pw.nW, C.pair_cap, pw.b0);
+        return PGX_ERR_CAPACITY;
+    }
+    if (pw.nW > pw.hW->cap) {  // the host buffer was too small: grow it and fetch again (the window's stream is idle by now)
+        PGX_HIP(pw.hW->reserve(pw.nW));  // (reserve keeps nothing: copy the whole range again)
+        PGX_HIP(hipMemcpyAsync(pw.hW->p, ws.pairsW, (size_t)pw.nW * sizeof(Pair), hipMemcpyDeviceToHost, ws.st));
+        PGX_HIP(spin_sync(ws.st));
+    }
+    return PGX_OK;
+}
+
+// The window's bookkeeping -- winners, numbering of the new representatives, identities, the candidates
+// the one-by-one pass would have examined, the outputs -- works on the host copies only.
+int finish_window(ClusterCall &C, PendingWindow &pw) {
+    if (C.overlap) { int rc = wait_closed(C, pw); if (rc) return rc; }
+    const uint32_t b0 = pw.b0, nb = pw.nb, n = C.n;
+    pgx_cluster_stats &S = C.S;
+    uint8_t *const status = C.status.data();
+    unsigned long long *const winner_key = C.winner_key.data();
+    C.pending_words = 0;
+    // members that were never in a block: their winner is the 64-bit minimum in best[]
+    for (uint32_t q = 0; q < nb; ++q) {
+        if (status[q] != ST_OPEN) continue;
+        const unsigned long long key = pw.h_best->p[q];
+        if (key == kNoBest) {
+            if (pw.sweep) { status[q] = ST_NONE; continue; }   // no representative in the table being dropped
+            pgx_set_error("pgx_cluster_greedy: unresolved member after the last block"); return PGX_ERR_INTERNAL;
+        }
+        status[q] = ST_MEMBER;
+        winner_key[q] = key;
+        C.strand_of[b0 + q] = (uint8_t)(key >> 63);
+        if (pw.sweep) C.h_taken.p[b0 + q] = 1;
+    }
+    if (C.both)  // reverse-strand word walks happen only for queries the forward strand did not place
+        for (uint32_t q = 0; q < nb; ++q)
+            if (status[q] == ST_REP || status[q] == ST_NONE || (status[q] == ST_MEMBER && (winner_key[q] >> 63))) C.visits_rc += C.h_rcvis.p[q];
+    // new representatives are numbered in sequence order
+    for (uint32_t q = 0; q < nb; ++q)
+        if (status[q] == ST_REP) {
+            C.cluster_of[b0 + q] = (int32_t)C.rep_seq.size();
+            C.rep_seq.push_back(b0 + q);
+            S.sum_len_reps += C.h_len[b0 + q];
+            S.rep_words += C.h_wcnt[b0 + q];
+        }
+    for (uint32_t q = 0; q < nb; ++q)
+        if (status[q] == ST_MEMBER) C.cluster_of[b0 + q] = C.cluster_of[(uint32_t)winner_key[q] & 0x7FFFFFFFu];
+    account(C, pw.hW->p, pw.nW);
+    PairCounts examined;
+    const bool fits = finish_window_pairs(pw.hW->p, pw.nW, b0, n, status, winner_key, C.h_len.data(), C.iden_of.data(), examined);
+    add_counts(S, examined);
+    if (!fits) return band_error();
+    // the window's outputs, in the caller's order; member numbers follow the sorted order (A.3)
+    C.members.resize(C.rep_seq.size(), 0u);
+    for (uint32_t q = 0; q < nb; ++q) {
+        if (status[q] == ST_ABSENT || status[q] == ST_NONE) continue;   // (written when placed / not placed yet)
+        const uint32_t k = b0 + q, o = C.order[k];
+        const int32_t c = C.cluster_of[k];
+        C.out_cluster[o] = c;
+        C.out_member[o] = (int32_t)C.members[(size_t)c]++;
+        C.out_identity[o] = C.iden_of[k] >= 0 ? (float)C.iden_of[k] / (float)C.h_len[k] : 0.f;
+        if (C.out_strand) C.out_strand[o] = C.strand_of[k];   // (set for members only)
+    }
+    return PGX_OK;
+}
+
+int run_pending(ClusterCall &C) {   // the bookkeeping of the window before, if it has not run
+    if (!C.pending.pending) return PGX_OK;
+    C.pending.pending = false;
+    return finish_window(C, C.pending);
+}
+
+int drain(ClusterCall &C) {     // nothing in flight, no bookkeeping pending
+    { int rc = run_pending(C); if (rc) return rc; }
+    PGX_HIP(hipStreamSynchronize(C.st_main));
+    PGX_HIP(hipStreamSynchronize(C.ctx->stream2));
+    return PGX_OK;
+}
+
+// the host side of a window starts with the bookkeeping of the window before (deferred behind this window's
+// first kernels), then the member states
+int begin_host_side(ClusterCall &C, Window &W) {
+    { int rc = run_pending(C); if (rc) return rc; }
+    for (uint32_t q = 0; q < W.nb; ++q) C.status[q] = C.cluster_of[W.b0 + q] >= 0 ? ST_ABSENT : ST_OPEN;
+    return PGX_OK;
+}
+
+// ========================================================================================
+// the phases, in the order of a call
+// ========================================================================================
+int check_params(const ClusterCall &C, const int32_t *out_cluster, const int32_t *out_member, const float *out_identity) {
+    const pgx_cluster_params *P = C.P;
+    const pgx_ctx *ctx = C.ctx;
+    CL_REQUIRE(C.n_in == 0 || (C.d_residues && C.d_offsets), "NULL sequence arrays");
+    CL_REQUIRE(out_cluster && out_member && out_identity, "NULL output arrays");
+    CL_REQUIRE(P->alphabet == 0 || P->alphabet == 1, "alphabet must be 0 (protein) or 1 (nucleotide)");
+    CL_REQUIRE(P->word_len >= 2 && P->word_len <= (C.nt ? 11 : kMaxWordLen), "word_len must be 2..5 (protein) or 2..11 (nucleotide)");
+    CL_REQUIRE(P->identity >= 0.4 && P->identity <= 1.0, "identity must be 0.4..1.0");
+    CL_REQUIRE(P->band_width >= 1 && P->band_width <= kMaxBand, "band_width must be 1..64");
+    CL_REQUIRE(P->min_length >= P->word_len - 1, "min_length must be at least word_len - 1");
+    CL_REQUIRE(P->batch_size >= 0, "batch_size must not be negative");
+    CL_REQUIRE(P->shard_count >= 0 && (P->shard_count == 0 ? P->shard_index == 0 : (P->shard_index >= 0 && P->shard_index < P->shard_count)),
+               "shard_index must be in [0, shard_count)");
+    CL_REQUIRE(P->shard_count <= 1 || C.exchanging, "shard_count > 1 needs an exchange callback or a communicator (pgx_rccl_comm_create)");
+    CL_REQUIRE(!C.native_exchange || (ctx->comm_world == P->shard_count && ctx->comm_rank == P->shard_index),
+               "shard_index / shard_count differ from the rank / size of the context's communicator");
+    CL_REQUIRE(!P->exchange || (P->exchange_send && P->exchange_recv),
+               "the exchange callback needs exchange_send / exchange_recv (2 slots of PGX_EXCHANGE_WORDS uint64 per process, device memory)");
+    PGX_HIP(hipSetDevice(ctx->device_id));
+    return PGX_OK;
+}
+
+// ---- A.2 / A.3: letters -> indices, stable descending-length order ---------------------
+// The GPU counts letters, orders the sequences and lays them out; the host sees the lengths as a histogram (one
+// small copy, one synchronisation) and derives its O(longest length) bookkeeping from that. Its per-sequence arrays
+// are filled behind the enqueued device work. Leaves n (0: nothing to cluster), max_len, len_hist, and for the host's
+// sort the order.
+int order_by_length(ClusterCall &C) {
+    pgx_ctx *ctx = C.ctx;
+    const pgx_cluster_params *P = C.P;
+    const hipStream_t st_main = C.st_main;
+    const uint32_t n_in = C.n_in;
+    const unsigned nth = C.nth;
+    for (int t = 0; t < P->word_len; ++t) C.n_codes *= C.nt ? 4u : (uint32_t)kNAA1;
     static_assert(kSegs == 4, "eight codes per word of the round's map");
-    const uint32_t bm_words = (n_codes / 8 + 2 + 3) & ~3u;   // words of the round's map of touched codes
-    const bool overlap = !nt && !std::getenv("PGX_NO_OVERLAP");   // consecutive windows on two streams, see below
-    DevBuf d_in_len(ctx, CL_SLOT_IN_LEN);
-    PGX_HIP(d_in_len.alloc((size_t)n_in * 4));
-    constexpr uint32_t kHistWords = H_BINS + kDevSortMaxLen + 1;
-    PGX_HIP(d_hist.alloc((size_t)kHistWords * 4));
-    PGX_HIP(d_idx.alloc(16));
-    PGX_HIP(d_newbits.alloc(2 * (size_t)bm_words * 4 + 16));          // two maps, used by alternate append rounds
+    C.bm_words = (C.n_codes / 8 + 2 + 3) & ~3u;   // words of the round's map of touched codes
+    DevBuf &d_counters = C.sets[0].counters_buf, &d_counters2 = C.sets[1].counters_buf;
+    PGX_HIP(C.d_in_len.alloc((size_t)n_in * 4));
+    PGX_HIP(C.d_hist.alloc((size_t)kHistWords * 4));
+    PGX_HIP(C.d_idx.alloc(16));
+    PGX_HIP(C.d_newbits.alloc(2 * (size_t)C.bm_words * 4 + 16));          // two maps, used by alternate append rounds
     PGX_HIP(d_counters.alloc(C_COUNT * 4));
-    PGX_HIP(d_visits.alloc(8));
-    if (overlap) PGX_HIP(d_counters2.alloc(C_COUNT * 4));
+    PGX_HIP(C.d_visits.alloc(8));
+    if (C.overlap) PGX_HIP(d_counters2.alloc(C_COUNT * 4));
+    C.sets[0].dc = d_counters.as<uint32_t>();
+    C.sets[1].dc = d_counters2.as<uint32_t>();
     {   // the call's small clears in one launch (a hipMemsetAsync each left the stream idle in between): the histogram,
         // the two round maps, the counters of both window sets, the visit counter; pool word 0 is never an array
         // (ovf == 0 means "no overflow array"), so the pool's cursor starts at 1
         ClearArgs ca{};
         auto seg = [&](DevBuf &b, size_t words) { ca.p[ca.n] = b.as<uint32_t>(); ca.words[ca.n] = (uint32_t)words; ++ca.n; };
-        seg(d_hist, kHistWords);
-        seg(d_newbits, 2 * (size_t)bm_words);
+        seg(C.d_hist, kHistWords);
+        seg(C.d_newbits, 2 * (size_t)C.bm_words);
         seg(d_counters, C_COUNT);
-        seg(d_visits, 2);
-        if (overlap) seg(d_counters2, C_COUNT);
-        ca.one = d_idx.as<uint32_t>();
-        clear_kernel<<<1024, 256, 0, st>>>(ca);
+        seg(C.d_visits, 2);
+        if (C.overlap) seg(d_counters2, C_COUNT);
+        ca.one = C.d_idx.as<uint32_t>();
+        clear_kernel<<<1024, 256, 0, st_main>>>(ca);
         LAUNCH_CHECK();
     }
     {
-        ProfScope prof(ctx, "seq_len_kernel", st);
-        seq_len_kernel<<<(n_in + 3) / 4, 256, 0, st>>>(d_residues, d_offsets, n_in, total_in, d_in_len.as<uint32_t>());
-        len_hist_kernel<<<std::min(64u, (n_in + 1023u) / 1024u), 1024, 0, st>>>(d_in_len.as<uint32_t>(), n_in, P->min_length,
-                                                                               d_hist.as<uint32_t>());
+        ProfScope prof(ctx, "seq_len_kernel", st_main);
+        seq_len_kernel<<<(n_in + 3) / 4, 256, 0, st_main>>>(C.d_residues, C.d_offsets, n_in, C.total_in, C.d_in_len.as<uint32_t>());
+        len_hist_kernel<<<std::min(64u, (n_in + 1023u) / 1024u), 1024, 0, st_main>>>(C.d_in_len.as<uint32_t>(), n_in, P->min_length,
+                                                                                    C.d_hist.as<uint32_t>());
     }
     LAUNCH_CHECK();
-    // (the per-sequence host arrays live in the context's scratch: no allocation, page faults or frees per call)
-    HostVec<uint32_t> h_hist(ctx, CL_HOST_HIST, kHistWords);
-    PGX_REQUIRE(h_hist.ok(), "out of host memory");
-    PGX_HIP(hipMemcpyAsync(h_hist.data(), d_hist.p, (size_t)(H_BINS + kHistLds) * 4, hipMemcpyDeviceToHost, st));
-    PGX_HIP(hipStreamSynchronize(st));
+    C.h_hist = HostVec<uint32_t>(ctx, CL_HOST_HIST, kHistWords);
+    HostVec<uint32_t> &h_hist = C.h_hist;
+    CL_REQUIRE(h_hist.ok(), "out of host memory");
+    PGX_HIP(hipMemcpyAsync(h_hist.data(), C.d_hist.p, (size_t)(H_BINS + kHistLds) * 4, hipMemcpyDeviceToHost, st_main));
+    PGX_HIP(hipStreamSynchronize(st_main));
     // PGX_HOST_PROLOGUE=1 takes the host's sort for any input (for comparisons)
-    const bool dev_sort = h_hist[H_OVER] == 0 && !std::getenv("PGX_HOST_PROLOGUE");
+    C.dev_sort = h_hist[H_OVER] == 0 && !std::getenv("PGX_HOST_PROLOGUE");
     uint32_t max_len = h_hist[H_MAX];
-    if (dev_sort && max_len >= kHistLds) {   // (rare: the bins the first copy left out)
-        PGX_HIP(hipMemcpyAsync(h_hist.data() + H_BINS + kHistLds, d_hist.as<uint32_t>() + H_BINS + kHistLds,
-                               (size_t)(max_len + 1 - kHistLds) * 4, hipMemcpyDeviceToHost, st));
-        PGX_HIP(hipStreamSynchronize(st));
+    if (C.dev_sort && max_len >= kHistLds) {   // (rare: the bins the first copy left out)
+        PGX_HIP(hipMemcpyAsync(h_hist.data() + H_BINS + kHistLds, C.d_hist.as<uint32_t>() + H_BINS + kHistLds,
+                               (size_t)(max_len + 1 - kHistLds) * 4, hipMemcpyDeviceToHost, st_main));
+        PGX_HIP(hipStreamSynchronize(st_main));
     }
-    phase("  seq_len + histogram + copy");
-    const uint32_t *len_hist = h_hist.data() + H_BINS;   // [L] = sequences of L letters that pass min_length
+    C.phase("  seq_len + histogram + copy");
+    C.len_hist = h_hist.data() + H_BINS;
     uint32_t n = 0;
-    HostVec<uint32_t> order(ctx, CL_HOST_ORDER, dev_sort ? 0 : n_in);   // (device sort: bound to n entries below)
-    std::vector<uint32_t> host_hist;
-    if (dev_sort) {
-        for (uint32_t L = 0; L <= max_len; ++L) n += len_hist[L];
+    C.order = HostVec<uint32_t>(ctx, CL_HOST_ORDER, C.dev_sort ? 0 : n_in);   // (device sort: bound to n entries by prepare_input)
+    if (C.dev_sort) {
+        for (uint32_t L = 0; L <= max_len; ++L) n += C.len_hist[L];
     } else {
         // a sequence beyond kDevSortMaxLen: the lengths come to the host, which sorts them and uploads the order
         HostVec<uint32_t> in_len(ctx, CL_HOST_IN_LEN, n_in);
-        PGX_REQUIRE(in_len.ok() && order.ok(), "out of host memory");
-        PGX_HIP(hipMemcpyAsync(in_len.data(), d_in_len.p, (size_t)n_in * 4, hipMemcpyDeviceToHost, st));
-        PGX_HIP(hipStreamSynchronize(st));
+        HostVec<uint32_t> &order = C.order;
+        CL_REQUIRE(in_len.ok() && order.ok(), "out of host memory");
+        PGX_HIP(hipMemcpyAsync(in_len.data(), C.d_in_len.p, (size_t)n_in * 4, hipMemcpyDeviceToHost, st_main));
+        PGX_HIP(hipStreamSynchronize(st_main));
         max_len = 0;
         {
             std::vector<uint32_t> mx(nth, 0u);
@@ -2666,1005 +3121,642 @@ static int cluster_greedy_impl(pgx_ctx *ctx, const uint8_t *d_residues, const ui
             for (size_t i = b; i < e; ++i)
                 if ((int)in_len[i] > P->min_length) h[max_len - in_len[i]]++;
         });
-        host_hist.assign((size_t)max_len + 1, 0u);
+        C.host_hist.assign((size_t)max_len + 1, 0u);
         for (size_t l = 0; l <= max_len; ++l)
             for (unsigned t = 0; t < nth; ++t) {
                 const uint32_t c = bucket[n_bkt * t + l];
-                bucket[n_bkt * t + l] = n; n += c; host_hist[max_len - l] += c;
+                bucket[n_bkt * t + l] = n; n += c; C.host_hist[max_len - l] += c;
             }
         parallel_for(n_in, nth, [&](unsigned t, size_t b, size_t e) {
             uint32_t *h = bucket.data() + n_bkt * t;
             for (size_t i = b; i < e; ++i)
                 if ((int)in_len[i] > P->min_length) order[h[max_len - in_len[i]]++] = (uint32_t)i;
         });
-        len_hist = host_hist.data();
+        C.len_hist = C.host_hist.data();
     }
-    if (n == 0) { if (stats) *stats = S; return PGX_OK; }
-    PGX_REQUIRE(n < (1u << 30), "too many sequences for the index entries (30 bits)");
-    uint32_t mshift = 8;                         // smallest field that holds n (and the strike-out value above it)
-    while ((1u << mshift) <= n) ++mshift;
-    if (dev_sort) order = HostVec<uint32_t>(ctx, CL_HOST_ORDER, n);   // (arrives behind the device's sort, read when outputs are written)
+    C.n = n;
+    C.max_len = max_len;
+    return PGX_OK;
+}
+
+// Run tables, thresholds, the windows' capacities, the device buffers; then enqueued: the device's sort (or the upload
+// of the host's), the layout, encode / reverse complement / pack, the per-sequence thresholds.
+int prepare_input(ClusterCall &C) {
+    pgx_ctx *ctx = C.ctx;
+    const pgx_cluster_params *P = C.P;
+    const hipStream_t st_main = C.st_main;
+    const bool nt = C.nt, both = C.both;
+    const uint32_t n = C.n, n_in = C.n_in, max_len = C.max_len;
+    CL_REQUIRE(n < (1u << 30), "too many sequences for the index entries (30 bits)");
+    while ((1u << C.mshift) <= n) ++C.mshift;   // smallest field that holds n (and the strike-out value above it)
+    if (C.dev_sort) C.order = HostVec<uint32_t>(ctx, CL_HOST_ORDER, n);   // (arrives behind the device's sort, read when outputs are written)
 
     // sequences n .. 2n-1 are the reverse complements (nucleotides, both strands)
-    const uint32_t nv = both ? 2 * n : n;
-    HostVec<uint64_t> h_off(ctx, CL_HOST_OFF, (size_t)nv + 1);
-    HostVec<uint32_t> h_len(ctx, CL_HOST_LEN, nv);
-    PGX_REQUIRE(order.ok() && h_off.ok() && h_len.ok(), "out of host memory");
+    const uint32_t nv = C.nv = both ? 2 * n : n;
+    C.h_off = HostVec<uint64_t>(ctx, CL_HOST_OFF, (size_t)nv + 1);
+    C.h_len = HostVec<uint32_t>(ctx, CL_HOST_LEN, nv);
+    CL_REQUIRE(C.order.ok() && C.h_off.ok() && C.h_len.ok(), "out of host memory");
     // The sorted list is one run of equal lengths per histogram bucket: run r holds the sequences of max_len - r
     // letters. Its first sorted position, residue offset and packed-word offset are prefix sums over the buckets; inside
-    // a run offsets advance by the length. The device (layout_kernel) and the host (below, behind the enqueued work)
-    // expand the same tables.
-    const uint32_t n_runs = max_len + 1;
-    HostVec<uint64_t> h_runs(ctx, CL_HOST_RUNS, 2 * ((size_t)n_runs + 1));
-    PGX_REQUIRE(h_runs.ok(), "out of host memory");
-    uint64_t *const run_off = h_runs.data();
-    uint32_t *const run_pos = reinterpret_cast<uint32_t *>(run_off + n_runs + 1), *const run_pk = run_pos + n_runs + 1;
-    if ((both ? 2 : 1) * build_run_tables(len_hist, max_len, run_off, run_pos, run_pk) > 0xFFFFFFF0ull) {
+    // a run offsets advance by the length. The device (layout_kernel) and the host (plan_windows, behind the enqueued
+    // work) expand the same tables.
+    const uint32_t n_runs = C.n_runs = max_len + 1;
+    C.h_runs = HostVec<uint64_t>(ctx, CL_HOST_RUNS, 2 * ((size_t)n_runs + 1));
+    CL_REQUIRE(C.h_runs.ok(), "out of host memory");
+    C.run_off = C.h_runs.data();
+    C.run_pos = reinterpret_cast<uint32_t *>(C.run_off + n_runs + 1);
+    C.run_pk = C.run_pos + n_runs + 1;
+    if ((both ? 2 : 1) * build_run_tables(C.len_hist, max_len, C.run_off, C.run_pos, C.run_pk) > 0xFFFFFFF0ull) {
         pgx_set_error("pgx_cluster_greedy: too many residues for 32-bit packed offsets");
         return PGX_ERR_CAPACITY;
     }
-    const uint64_t total = (both ? 2 : 1) * run_off[n_runs];   // residues and packed words of all nv sequences
-    const uint64_t total_pk = (uint64_t)(both ? 2 : 1) * run_pk[n_runs];
-    auto fill_host_layout = [&]() {   // h_len, h_off from the run tables
-        parallel_for(nv, nth, [&](unsigned, size_t b, size_t e) {
-            expand_runs(run_off, run_pos, max_len, n, b, e, h_len.data(), h_off.data());
-        });
-        h_off[nv] = total;
-    };
-    phase(dev_sort ? "  run tables" : "  host sort + run tables");
-    // per-query thresholds in double, exactly as the sequential rule computes them
-    // They depend on the length only: one small table per threshold (host, in double), expanded per sequence on
-    // the device (thresholds_kernel) instead of three host passes and three uploads of n integers.
-    HostVec<int32_t> h_thr(ctx, CL_HOST_THR, 3 * ((size_t)max_len + 1));
-    PGX_REQUIRE(h_thr.ok(), "out of host memory");
+    const uint64_t total = C.total = (both ? 2 : 1) * C.run_off[n_runs];   // residues and packed words of all nv sequences
+    const uint64_t total_pk = C.total_pk = (uint64_t)(both ? 2 : 1) * C.run_pk[n_runs];
+    C.phase(C.dev_sort ? "  run tables" : "  host sort + run tables");
+    // One small table per threshold (host, in double), expanded per sequence on the device (thresholds_kernel) instead
+    // of three host passes and three uploads of n integers.
+    C.h_thr = HostVec<int32_t>(ctx, CL_HOST_THR, 3 * ((size_t)max_len + 1));
+    CL_REQUIRE(C.h_thr.ok(), "out of host memory");
     {
-        int32_t *t_aa1 = h_thr.data(), *t_aas = t_aa1 + max_len + 1, *t_aan = t_aas + max_len + 1;
-        for (uint32_t L = 0; L <= max_len; ++L) {
-            const int len = (int)L;
-            const int aa1 = (int)(P->identity * (double)len);
-            t_aa1[L] = aa1;
-            if (P->identity > 0.95) {
-                t_aas[L] = len - (nt ? 4 : 2) + 1 - (len - aa1) * (nt ? 4 : 2);
-                t_aan[L] = len - P->word_len + 1 - (len - aa1) * P->word_len;
-            } else {
-                t_aas[L] = (int)(P->aas_cutoff * (double)len);
-                t_aan[L] = (int)(P->aan_cutoff * (double)len);
-            }
-        }
+        int32_t *t_aa1 = C.h_thr.data(), *t_aas = t_aa1 + max_len + 1, *t_aan = t_aas + max_len + 1;
+        threshold_tables(P->identity, P->word_len, P->aas_cutoff, P->aan_cutoff, nt, max_len, t_aa1, t_aas, t_aan);
         for (uint32_t L = 0; L <= max_len; ++L)   // (the lengths that occur)
-            PGX_REQUIRE(!(len_hist[L] && t_aas[L] < 1), "aas_cutoff too small: every sequence needs required_aas >= 1");
-        S.sum_len_queries = run_off[n_runs];
+            CL_REQUIRE(!(C.len_hist[L] && t_aas[L] < 1), "aas_cutoff too small: every sequence needs required_aas >= 1");
+        C.S.sum_len_queries = C.run_off[n_runs];
     }
-    S.n_clustered = n;
+    C.S.n_clustered = n;
 
     // ---- device buffers ------------------------------------------------------------------
-    const uint32_t window_cap = pgx_cluster_window_cap(P);           // queries per window
-    PGX_REQUIRE(!exchanging || window_cap <= PGX_EXCHANGE_KEYS, "window larger than PGX_EXCHANGE_KEYS");
-    uint32_t pair_cap = 4u << 20;  // grows per window for nucleotides, whose word filter passes almost every pair
+    const uint32_t window_cap = C.window_cap = pgx_cluster_window_cap(P);           // queries per window
+    CL_REQUIRE(!C.exchanging || window_cap <= PGX_EXCHANGE_KEYS, "window larger than PGX_EXCHANGE_KEYS");
     // blocks: nucleotide rules pass nearly every pair, so 512 members (all their pairs fit); proteins 4096
-    uint32_t block_cap = std::min(nt ? 512u : kBlockCap, window_cap);
-    const uint32_t pair_cap_k = nt ? 512u * 512u + 16u : (1u << 20);
+    C.block_cap = std::min(nt ? 512u : kBlockCap, window_cap);
+    const uint32_t pair_cap_k = C.pair_cap_k = nt ? 512u * 512u + 16u : (1u << 20);
     // A window = consecutive members: at most window_cap of them, in at most kMaxChunks chunks of bounded word
     // volume (see certain_kernel: the words of one chunk must cover a fraction of the code space well below
     // the word threshold fraction, or unrelated members alone would defeat the discovery test).
-    const double thr_frac = P->identity > 0.95 ? std::max(0.0, 1.0 - (1.0 - P->identity) * P->word_len) : P->aan_cutoff;
+    C.thr_frac = P->identity > 0.95 ? std::max(0.0, 1.0 - (1.0 - P->identity) * P->word_len) : P->aan_cutoff;
     // (a code space too small for that -- nucleotide 5-mers, tiny thresholds -- gets one chunk per window: the
     // discovery test then certifies little and the exact block resolution does the work)
-    // (0.8 of the threshold fraction: unrelated members alone then share 17 % of their words with a chunk by chance,
-    // against a threshold of 23 %. Measured, cfg-3s / cfg-4 / 300,000 unrelated random proteins: 0.4 -> 101 ms / 1.57 s /
-    // 49 ms, 0.8 -> 94 ms / 1.3 s / 64 ms, 1.0 -> 93 ms / 1.26 s / 82 ms -- families fill far less of the code space than
-    // their word count, so larger chunks mean fewer, larger windows; without families the test starts to fail.)
-    static const double chunk_frac = std::getenv("PGX_CHUNK_FRAC") ? std::atof(std::getenv("PGX_CHUNK_FRAC")) : 0.8;
-    // The fraction ADAPTS: a window that needed three or more blocks (the discovery test certified too little: members
-    // without families) halves it for the windows after, a window with at most one block raises it again.
-    double cur_frac = chunk_frac;
-    uint64_t chunk_words = (uint64_t)(cur_frac * thr_frac * (double)n_codes);
-    const bool chunking = chunk_words >= 16384;
-    // cd-hit's memory-chunked rule (pgx.h): flush positions in the sorted list; a window never crosses one
-    std::vector<uint32_t> flush_at(P->chunk_boundaries, P->chunk_boundaries + (P->chunk_boundaries ? P->n_chunk_boundaries : 0u));
-    for (size_t i = 0; i < flush_at.size(); ++i)
-        PGX_REQUIRE(flush_at[i] > 0 && flush_at[i] < n && (i == 0 || flush_at[i] > flush_at[i - 1]),
-                    "chunk_boundaries must be strictly increasing positions in (0, number of clustered sequences)");
-    auto form_window = [&](uint32_t b0, Chunks &C, uint32_t limit) -> uint32_t {
-        C.n = 1; C.begin[0] = 0;
-        uint64_t in_chunk = 0;
-        uint32_t q = 0;
-        for (; b0 + q < limit && q < window_cap; ++q) {
-            const uint64_t w = h_len[b0 + q];
-            if (chunking && in_chunk && in_chunk + w > chunk_words) {
-                if (C.n == kMaxChunks) break;
-                C.begin[C.n++] = q;
-                in_chunk = 0;
-            }
-            in_chunk += w;
-        }
-        C.begin[C.n] = q;
-        return q;
-    };
-    const bool need_gscratch = (uint64_t)max_len * 2 > kDiagLdsSmall;
-    const uint32_t packed_len = nt ? kPackedLenNt : kPackedLenAa;   // queries beyond this: 64-bit histogram cells
-    const uint32_t gs_cells = (max_len + 64u) & ~63u;
+    C.cur_frac = chunk_frac_default();
+    C.chunk_words = (uint64_t)(C.cur_frac * C.thr_frac * (double)C.n_codes);
+    C.chunking = C.chunk_words >= 16384;
+    C.flush_at.assign(P->chunk_boundaries, P->chunk_boundaries + (P->chunk_boundaries ? P->n_chunk_boundaries : 0u));
+    for (size_t i = 0; i < C.flush_at.size(); ++i)
+        CL_REQUIRE(C.flush_at[i] > 0 && C.flush_at[i] < n && (i == 0 || C.flush_at[i] > C.flush_at[i - 1]),
+                   "chunk_boundaries must be strictly increasing positions in (0, number of clustered sequences)");
+    C.need_gscratch = (uint64_t)max_len * 2 > kDiagLdsSmall;
+    C.packed_len = nt ? kPackedLenNt : kPackedLenAa;   // queries beyond this: 64-bit histogram cells
+    C.gs_cells = (max_len + 64u) & ~63u;
     // per workgroup: 2 L diagonals (one or two words each) + L query positions
-    const uint32_t gs_stride = (max_len > packed_len ? 5u : 3u) * gs_cells;
+    C.gs_stride = (max_len > C.packed_len ? 5u : 3u) * C.gs_cells;
     // diag: one wave per pair, ~11 workgroups fit a CU; giant sequences: fewer workgroups, at most ~4 GB of scratch
-    const uint32_t diag_grid = (uint32_t)std::max<uint64_t>(64, std::min<uint64_t>(8192, (4ull << 30) / ((uint64_t)gs_stride * 4)));
-    const uint32_t align_grid = 1024;
+    C.diag_grid = (uint32_t)std::max<uint64_t>(64, std::min<uint64_t>(8192, (4ull << 30) / ((uint64_t)C.gs_stride * 4)));
 
-    PGX_HIP(d_res.alloc(total + 16));
-    PGX_HIP(d_off.alloc(((size_t)nv + 1) * 8));
-    PGX_HIP(d_len.alloc((size_t)nv * 4));
-    PGX_HIP(d_wcode.alloc((total + 16) * 4));
-    PGX_HIP(d_wmult.alloc((total + 16) * 2));
-    PGX_HIP(d_wcnt.alloc((size_t)nv * 4));
-    PGX_HIP(d_pk.alloc(((size_t)total_pk + 16) * 4));
-    PGX_HIP(d_pkoff.alloc(((size_t)nv + 1) * 4));
-    PGX_HIP(d_aa1.alloc((size_t)n * 4));
-    PGX_HIP(d_aas.alloc((size_t)n * 4));
-    PGX_HIP(d_aan.alloc((size_t)n * 4));
+    PGX_HIP(C.d_res.alloc(total + 16));
+    PGX_HIP(C.d_off.alloc(((size_t)nv + 1) * 8));
+    PGX_HIP(C.d_len.alloc((size_t)nv * 4));
+    PGX_HIP(C.d_wcode.alloc((total + 16) * 4));
+    PGX_HIP(C.d_wmult.alloc((total + 16) * 2));
+    PGX_HIP(C.d_wcnt.alloc((size_t)nv * 4));
+    PGX_HIP(C.d_pk.alloc(((size_t)total_pk + 16) * 4));
+    PGX_HIP(C.d_pkoff.alloc(((size_t)nv + 1) * 4));
+    PGX_HIP(C.d_aa1.alloc((size_t)n * 4));
+    PGX_HIP(C.d_aas.alloc((size_t)n * 4));
+    PGX_HIP(C.d_aan.alloc((size_t)n * 4));
     // the word index: all lines empty (one memset of n_codes * 128 B per call, e.g. 523 MB for protein 5-mers)
-    PGX_HIP(d_lines.alloc((size_t)n_codes * sizeof(IndexLine)));
-    PGX_HIP(hipMemsetAsync(d_lines.p, 0, (size_t)n_codes * sizeof(IndexLine), st));
-    PGX_HIP(d_best_own.alloc((size_t)window_cap * 8));
-    PGX_HIP(d_rcvis.alloc((size_t)window_cap * 8));
-    PGX_HIP(d_blk_list.alloc((size_t)kBlockCap * 4));
-    PGX_HIP(d_ulist.alloc((size_t)window_cap * 4));
-    PGX_HIP(d_new_list.alloc((size_t)window_cap * 4));
-    PGX_HIP(d_flags.alloc(4 * (size_t)window_cap));  // done, in-block, has-candidate, accepted
-    PGX_HIP(d_list.alloc((size_t)pair_cap_k * 4));
-    PGX_HIP(d_gather.alloc((size_t)pair_cap_k * sizeof(Pair)));
-    PGX_HIP(d_pairsW.alloc((size_t)pair_cap * sizeof(Pair)));
-    PGX_HIP(d_pairsK.alloc((size_t)pair_cap_k * sizeof(Pair)));
-    if (need_gscratch) PGX_HIP(d_gscratch.alloc((size_t)diag_grid * gs_stride * 4));
-    // Consecutive windows overlap on two streams (proteins, one process): the tail of window w -- the pass over
-    // all members after its last block, that pass's diagonal tests and alignments, the close -- only READS the
-    // index, and so does phase A of window w+1. Each window therefore has its own counters, best keys, member flags,
-    // pair records and host copies (two sets, used alternately); window w+1 starts when the index of window w is
-    // final (event after its last strike-out) and appends to the index only after window w's close (second event).
-    // A few hundred pairs per evaluation keep a 60-us dependent chain per alignment on the path otherwise.
-    // (Record-sharded mode too: the exchange buffers have one slot per window in flight, and every process enqueues its
-    // collectives in the same order because the host logic is the same function of replicated results.)
-    if (overlap) {
-        if (!exchanging) PGX_HIP(d_best2.alloc((size_t)window_cap * 8));
-        PGX_HIP(d_flags2.alloc(4 * (size_t)window_cap));
-        PGX_HIP(d_pairsW2.alloc((size_t)pair_cap * sizeof(Pair)));
-        if (need_gscratch) PGX_HIP(d_gscratch2.alloc((size_t)diag_grid * gs_stride * 4));
+    PGX_HIP(C.d_lines.alloc((size_t)C.n_codes * sizeof(IndexLine)));
+    PGX_HIP(hipMemsetAsync(C.d_lines.p, 0, (size_t)C.n_codes * sizeof(IndexLine), st_main));
+    PGX_HIP(C.sets[0].best_buf.alloc((size_t)window_cap * 8));
+    PGX_HIP(C.d_rcvis.alloc((size_t)window_cap * 8));
+    PGX_HIP(C.d_blk_list.alloc((size_t)kBlockCap * 4));
+    PGX_HIP(C.d_ulist.alloc((size_t)window_cap * 4));
+    PGX_HIP(C.d_new_list.alloc((size_t)window_cap * 4));
+    PGX_HIP(C.sets[0].flags_buf.alloc(4 * (size_t)window_cap));  // done, in-block, has-candidate, accepted
+    PGX_HIP(C.d_list.alloc((size_t)pair_cap_k * 4));
+    PGX_HIP(C.d_gather.alloc((size_t)pair_cap_k * sizeof(Pair)));
+    PGX_HIP(C.sets[0].pairs_buf.alloc((size_t)C.pair_cap * sizeof(Pair)));
+    PGX_HIP(C.d_pairsK.alloc((size_t)pair_cap_k * sizeof(Pair)));
+    if (C.need_gscratch) PGX_HIP(C.sets[0].gscratch_buf.alloc((size_t)C.diag_grid * C.gs_stride * 4));
+    if (C.overlap) {   // the second set of a window's own state, see WindowSet
+        if (!C.exchanging) PGX_HIP(C.sets[1].best_buf.alloc((size_t)window_cap * 8));
+        PGX_HIP(C.sets[1].flags_buf.alloc(4 * (size_t)window_cap));
+        PGX_HIP(C.sets[1].pairs_buf.alloc((size_t)C.pair_cap * sizeof(Pair)));
+        if (C.need_gscratch) PGX_HIP(C.sets[1].gscratch_buf.alloc((size_t)C.diag_grid * C.gs_stride * 4));
     }
-    // overflow pool of the index: sized before every window from the entries that exist and the most the
-    // window can add (every array is re-allocated with twice the need: <= 8 words per entry in all)
-    int pool_cur = 0;
-    uint64_t pool_cap = 0;
-    auto ensure_pool = [&](uint64_t entries, hipStream_t on) -> int {
-        const uint64_t need = 8 * entries + 4096;
-        if (need <= pool_cap) return PGX_OK;
-        if (need > 0xFFFFFFF0ull) { pgx_set_error("pgx_cluster_greedy: word index too large for 32-bit pool offsets"); return PGX_ERR_CAPACITY; }
-        const uint64_t want = std::min<uint64_t>(0xFFFFFFF0ull, need + need / 2);
-        DevBuf &nb_ = d_pool[pool_cur ^ 1];
-        PGX_HIP(nb_.alloc(want * 4));
-        if (pool_cap) PGX_HIP(hipMemcpyAsync(nb_.p, d_pool[pool_cur].p, pool_cap * 4, hipMemcpyDeviceToDevice, on));
-        pool_cur ^= 1;
-        pool_cap = want;
-        return PGX_OK;
-    };
-    PGX_HIP(d_order.alloc((size_t)n * 4));
-    if (dev_sort) {
+    PGX_HIP(C.d_order.alloc((size_t)n * 4));
+    if (C.dev_sort) {
         // stable counting sort on the device: a share of the input per wave, the smallest that keeps the
         // (length, share) counters within kSortCells
         uint32_t per = kSortShare;
         while ((uint64_t)((n_in + per - 1) / per) * n_runs > kSortCells) per *= 2;
         const uint32_t n_shares = (n_in + per - 1) / per, cells = n_shares * n_runs, tiles = (cells + kScanTile - 1) / kScanTile;
-        PGX_HIP(d_sortcnt.alloc((size_t)cells * 4));
-        PGX_HIP(d_tilesum.alloc((size_t)tiles * 4));
-        uint32_t *const cnt = d_sortcnt.as<uint32_t>(), *const in_len = d_in_len.as<uint32_t>();
-        ProfScope prof(ctx, "length_sort_kernels", st);
+        PGX_HIP(C.d_sortcnt.alloc((size_t)cells * 4));
+        PGX_HIP(C.d_tilesum.alloc((size_t)tiles * 4));
+        uint32_t *const cnt = C.d_sortcnt.as<uint32_t>(), *const in_len = C.d_in_len.as<uint32_t>();
+        ProfScope prof(ctx, "length_sort_kernels", st_main);
         ClearArgs ca{};
         ca.p[0] = cnt; ca.words[0] = cells; ca.n = 1;
-        clear_kernel<<<std::min(2048u, (cells + 255u) / 256u), 256, 0, st>>>(ca);
-        sort_count_kernel<<<(n_in + 255) / 256, 256, 0, st>>>(in_len, n_in, P->min_length, max_len, per, n_shares, cnt);
-        tile_sum_kernel<<<tiles, 256, 0, st>>>(cnt, cells, d_tilesum.as<uint32_t>());
-        tile_scan_kernel<<<tiles, 256, 0, st>>>(cnt, cells, d_tilesum.as<uint32_t>());
-        sort_place_kernel<<<(n_shares + 3) / 4, 256, 0, st>>>(in_len, n_in, P->min_length, max_len, per, n_shares, cnt, n,
-                                                              d_order.as<uint32_t>());
+        clear_kernel<<<std::min(2048u, (cells + 255u) / 256u), 256, 0, st_main>>>(ca);
+        sort_count_kernel<<<(n_in + 255) / 256, 256, 0, st_main>>>(in_len, n_in, P->min_length, max_len, per, n_shares, cnt);
+        tile_sum_kernel<<<tiles, 256, 0, st_main>>>(cnt, cells, C.d_tilesum.as<uint32_t>());
+        tile_scan_kernel<<<tiles, 256, 0, st_main>>>(cnt, cells, C.d_tilesum.as<uint32_t>());
+        sort_place_kernel<<<(n_shares + 3) / 4, 256, 0, st_main>>>(in_len, n_in, P->min_length, max_len, per, n_shares, cnt, n,
+                                                                   C.d_order.as<uint32_t>());
         LAUNCH_CHECK();
         // (the host reads the order when it writes a window's outputs, behind kernels enqueued after this copy)
-        PGX_HIP(hipMemcpyAsync(order.data(), d_order.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+        PGX_HIP(hipMemcpyAsync(C.order.data(), C.d_order.p, (size_t)n * 4, hipMemcpyDeviceToHost, st_main));
     } else {
-        PGX_HIP(hipMemcpyAsync(d_order.p, order.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+        PGX_HIP(hipMemcpyAsync(C.d_order.p, C.order.data(), (size_t)n * 4, hipMemcpyHostToDevice, st_main));
     }
     {   // lengths, offsets and packed offsets of the sorted list, both halves, from the run tables
         const size_t runs_bytes = 2 * ((size_t)n_runs + 1) * 8;
-        PGX_HIP(d_runs.alloc(runs_bytes));
-        PGX_HIP(hipMemcpyAsync(d_runs.p, h_runs.data(), runs_bytes, hipMemcpyHostToDevice, st));
-        const uint64_t *const dr_off = d_runs.as<uint64_t>();
+        PGX_HIP(C.d_runs.alloc(runs_bytes));
+        PGX_HIP(hipMemcpyAsync(C.d_runs.p, C.h_runs.data(), runs_bytes, hipMemcpyHostToDevice, st_main));
+        const uint64_t *const dr_off = C.d_runs.as<uint64_t>();
         const uint32_t *const dr_pos = reinterpret_cast<const uint32_t *>(dr_off + n_runs + 1), *const dr_pk = dr_pos + n_runs + 1;
-        layout_kernel<<<nv / 256 + 1, 256, 0, st>>>(dr_off, dr_pos, dr_pk, n_runs, max_len, n, nv, d_len.as<uint32_t>(),
-                                                    d_off.as<uint64_t>(), d_pkoff.as<uint32_t>());
+        layout_kernel<<<nv / 256 + 1, 256, 0, st_main>>>(dr_off, dr_pos, dr_pk, n_runs, max_len, n, nv, C.d_len.as<uint32_t>(),
+                                                         C.d_off.as<uint64_t>(), C.d_pkoff.as<uint32_t>());
         LAUNCH_CHECK();
     }
     {
-        ProfScope prof(ctx, "encode_gather_kernel", st);
-        encode_gather_kernel<<<(n + 3) / 4, 256, 0, st>>>(d_residues, d_offsets, d_order.as<uint32_t>(),
-                                                          d_off.as<uint64_t>(), d_res.as<uint8_t>(), n, nt ? 1 : 0);
+        ProfScope prof(ctx, "encode_gather_kernel", st_main);
+        encode_gather_kernel<<<(n + 3) / 4, 256, 0, st_main>>>(C.d_residues, C.d_offsets, C.d_order.as<uint32_t>(),
+                                                               C.d_off.as<uint64_t>(), C.d_res.as<uint8_t>(), n, nt ? 1 : 0);
         if (both)
-            revcomp_kernel<<<(n + 3) / 4, 256, 0, st>>>(d_res.as<uint8_t>(), d_off.as<uint64_t>(),
-                                                        d_len.as<uint32_t>(), n);
-        pack5_kernel<<<(nv + 3) / 4, 256, 0, st>>>(d_res.as<uint8_t>(), d_off.as<uint64_t>(), d_len.as<uint32_t>(),
-                                                   d_pkoff.as<uint32_t>(), nv, d_pk.as<uint32_t>());
+            revcomp_kernel<<<(n + 3) / 4, 256, 0, st_main>>>(C.d_res.as<uint8_t>(), C.d_off.as<uint64_t>(),
+                                                             C.d_len.as<uint32_t>(), n);
+        pack5_kernel<<<(nv + 3) / 4, 256, 0, st_main>>>(C.d_res.as<uint8_t>(), C.d_off.as<uint64_t>(), C.d_len.as<uint32_t>(),
+                                                        C.d_pkoff.as<uint32_t>(), nv, C.d_pk.as<uint32_t>());
     }
     LAUNCH_CHECK();
     {   // thresholds per sequence from the per-length tables
-        PGX_HIP(d_thr.alloc(3 * ((size_t)max_len + 1) * 4));
-        PGX_HIP(hipMemcpyAsync(d_thr.p, h_thr.data(), 3 * ((size_t)max_len + 1) * 4, hipMemcpyHostToDevice, st));
-        thresholds_kernel<<<(n + 255) / 256, 256, 0, st>>>(d_len.as<uint32_t>(), n, d_thr.as<int32_t>(), max_len + 1,
-                                                          d_aa1.as<int32_t>(), d_aas.as<int32_t>(), d_aan.as<int32_t>());
+        PGX_HIP(C.d_thr.alloc(3 * ((size_t)max_len + 1) * 4));
+        PGX_HIP(hipMemcpyAsync(C.d_thr.p, C.h_thr.data(), 3 * ((size_t)max_len + 1) * 4, hipMemcpyHostToDevice, st_main));
+        thresholds_kernel<<<(n + 255) / 256, 256, 0, st_main>>>(C.d_len.as<uint32_t>(), n, C.d_thr.as<int32_t>(), max_len + 1,
+                                                               C.d_aa1.as<int32_t>(), C.d_aas.as<int32_t>(), C.d_aan.as<int32_t>());
         LAUNCH_CHECK();
     }
-    phase("alloc + sort + layout + encode (enq)");
-    // ---- word lists: size classes are contiguous because the order is by length ----------
-    {
-        const int wl = P->word_len;
-        auto first_with_words_le = [&](uint32_t cap) { return pgxc::first_with_words_le(run_pos, max_len, cap, wl); };
-        const uint32_t k32 = first_with_words_le(32768), k8 = first_with_words_le(8192),
-                       k2 = first_with_words_le(2048), k1k = first_with_words_le(1023), k5 = first_with_words_le(512);
-        int rc;
-        uint8_t *r8 = d_res.as<uint8_t>(); uint64_t *o64 = d_off.as<uint64_t>(); uint32_t *l32 = d_len.as<uint32_t>();
-        uint32_t *wc = d_wcode.as<uint32_t>(); uint16_t *wm = d_wmult.as<uint16_t>(); uint32_t *wn = d_wcnt.as<uint32_t>();
-        const int base = nt ? 4 : kNAA1;
-        for (uint32_t half = 0; half < (both ? 2u : 1u); ++half) {  // the reverse complements have the same lengths
-            const uint32_t o = half * n;
-            if (k32) {   // giant sequences (more than 32768 words): a table in global memory, a few at a time
-                uint32_t slots = 65536;
-                while (slots < 2u * max_len) slots *= 2;
-                const uint32_t per_launch = std::min(k32, std::max(1u, (uint32_t)((256ull << 20) / ((uint64_t)slots * 8))));
-                PGX_HIP(d_hugewords.alloc((size_t)per_launch * slots * 8));
-                ProfScope prof(ctx, "words_kernel", st);
-                for (uint32_t a = 0; a < k32; a += per_launch)
-                    words_huge_kernel<<<std::min(per_launch, k32 - a), 1024, 0, st>>>(r8, o64, l32, o + a, o + std::min(k32, a + per_launch), wl, base,
-                                                                                       nt, d_hugewords.as<uint32_t>(), slots, wc, wm, wn,
-                                                                                       d_counters.as<uint32_t>() + C_ERR);
-                LAUNCH_CHECK();
-            }
-            if ((rc = launch_words<32768, 1024>(ctx, st, r8, o64, l32, o + k32, o + k8, wl, base, nt, wc, wm, wn))) return rc;
-            if ((rc = launch_words<8192, 1024>(ctx, st, r8, o64, l32, o + k8, o + k2, wl, base, nt, wc, wm, wn))) return rc;
-            if ((rc = launch_words_hash<2048, 256>(ctx, st, r8, o64, l32, o + k2, o + k1k, wl, base, nt, wc, wm, wn))) return rc;
-            if (k5 > k1k) {
-                ProfScope prof(ctx, "words_kernel", st);
-                words_wave_kernel<2048><<<(k5 - k1k + 3) / 4, 256, 0, st>>>(r8, o64, l32, o + k1k, o + k5, wl, base, nt, wc, wm, wn);
-                LAUNCH_CHECK();
-            }
-            if (n > k5) {
-                ProfScope prof(ctx, "words_kernel", st);
-                words_wave_kernel<1024><<<(n - k5 + 3) / 4, 256, 0, st>>>(r8, o64, l32, o + k5, o + n, wl, base, nt, wc, wm, wn);
-                LAUNCH_CHECK();
-            }
+    C.phase("alloc + sort + layout + encode (enq)");
+    return PGX_OK;
+}
+
+// ---- word lists: size classes are contiguous because the order is by length ----------
+int build_word_lists(ClusterCall &C) {
+    pgx_ctx *ctx = C.ctx;
+    const hipStream_t st_main = C.st_main;
+    const bool nt = C.nt;
+    const uint32_t n = C.n, max_len = C.max_len;
+    const int wl = C.P->word_len;
+    auto first_with_words_le = [&](uint32_t cap) { return pgxc::first_with_words_le(C.run_pos, max_len, cap, wl); };
+    const uint32_t k32 = first_with_words_le(32768), k8 = first_with_words_le(8192),
+                   k2 = first_with_words_le(2048), k1k = first_with_words_le(1023), k5 = first_with_words_le(512);
+    int rc;
+    uint8_t *r8 = C.d_res.as<uint8_t>(); uint64_t *o64 = C.d_off.as<uint64_t>(); uint32_t *l32 = C.d_len.as<uint32_t>();
+    uint32_t *wc = C.d_wcode.as<uint32_t>(); uint16_t *wm = C.d_wmult.as<uint16_t>(); uint32_t *wn = C.d_wcnt.as<uint32_t>();
+    const int base = nt ? 4 : kNAA1;
+    for (uint32_t half = 0; half < (C.both ? 2u : 1u); ++half) {  // the reverse complements have the same lengths
+        const uint32_t o = half * n;
+        if (k32) {   // giant sequences (more than 32768 words): a table in global memory, a few at a time
+            uint32_t slots = 65536;
+            while (slots < 2u * max_len) slots *= 2;
+            const uint32_t per_launch = std::min(k32, std::max(1u, (uint32_t)((256ull << 20) / ((uint64_t)slots * 8))));
+            PGX_HIP(C.d_hugewords.alloc((size_t)per_launch * slots * 8));
+            ProfScope prof(ctx, "words_kernel", st_main);
+            for (uint32_t a = 0; a < k32; a += per_launch)
+                words_huge_kernel<<<std::min(per_launch, k32 - a), 1024, 0, st_main>>>(r8, o64, l32, o + a, o + std::min(k32, a + per_launch), wl, base,
+                                                                                        nt, C.d_hugewords.as<uint32_t>(), slots, wc, wm, wn,
+                                                                                        C.sets[0].dc + C_ERR);
+            LAUNCH_CHECK();
+        }
+        if ((rc = launch_words<32768, 1024>(ctx, st_main, r8, o64, l32, o + k32, o + k8, wl, base, nt, wc, wm, wn))) return rc;
+        if ((rc = launch_words<8192, 1024>(ctx, st_main, r8, o64, l32, o + k8, o + k2, wl, base, nt, wc, wm, wn))) return rc;
+        if ((rc = launch_words_hash<2048, 256>(ctx, st_main, r8, o64, l32, o + k2, o + k1k, wl, base, nt, wc, wm, wn))) return rc;
+        if (k5 > k1k) {
+            ProfScope prof(ctx, "words_kernel", st_main);
+            words_wave_kernel<2048><<<(k5 - k1k + 3) / 4, 256, 0, st_main>>>(r8, o64, l32, o + k1k, o + k5, wl, base, nt, wc, wm, wn);
+            LAUNCH_CHECK();
+        }
+        if (n > k5) {
+            ProfScope prof(ctx, "words_kernel", st_main);
+            words_wave_kernel<1024><<<(n - k5 + 3) / 4, 256, 0, st_main>>>(r8, o64, l32, o + k5, o + n, wl, base, nt, wc, wm, wn);
+            LAUNCH_CHECK();
         }
     }
-    DevSeqs DS{d_res.as<uint8_t>(), d_off.as<uint64_t>(), d_len.as<uint32_t>(),
-               d_wcode.as<uint32_t>(), d_wmult.as<uint16_t>(), d_wcnt.as<uint32_t>(),
-               d_pk.as<uint32_t>(), d_pkoff.as<uint32_t>(), n, nt ? 4 : kNAA1, nt ? 4 : 2, nt ? 1 : 0, mshift};
-    HostVec<uint32_t> h_wcnt(ctx, CL_HOST_WCNT, n);
-    PGX_REQUIRE(h_wcnt.ok(), "out of host memory");
-    PGX_HIP(hipMemcpyAsync(h_wcnt.data(), d_wcnt.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    C.DS = DevSeqs{C.d_res.as<uint8_t>(), C.d_off.as<uint64_t>(), C.d_len.as<uint32_t>(),
+                   C.d_wcode.as<uint32_t>(), C.d_wmult.as<uint16_t>(), C.d_wcnt.as<uint32_t>(),
+                   C.d_pk.as<uint32_t>(), C.d_pkoff.as<uint32_t>(), n, nt ? 4 : kNAA1, nt ? 4 : 2, nt ? 1 : 0, C.mshift};
+    C.h_wcnt = HostVec<uint32_t>(ctx, CL_HOST_WCNT, n);
+    CL_REQUIRE(C.h_wcnt.ok(), "out of host memory");
+    PGX_HIP(hipMemcpyAsync(C.h_wcnt.data(), C.d_wcnt.p, (size_t)n * 4, hipMemcpyDeviceToHost, st_main));
+    C.phase("word lists (enqueue)");
+    return PGX_OK;
+}
 
-    phase("word lists (enqueue)");
-    // ---- the host's copy of the layout, the windows' geometry (behind the enqueued work) ---
-    fill_host_layout();
-    phase("host lengths + offsets");
+// ---- the host's copy of the layout, the windows' geometry (behind the enqueued work), the window loop's buffers ---
+int plan_windows(ClusterCall &C) {
+    pgx_ctx *ctx = C.ctx;
+    const pgx_cluster_params *P = C.P;
+    const uint32_t n = C.n, nv = C.nv, max_len = C.max_len, window_cap = C.window_cap;
+    parallel_for(nv, C.nth, [&](unsigned, size_t b, size_t e) {   // h_len, h_off from the run tables
+        expand_runs(C.run_off, C.run_pos, max_len, n, b, e, C.h_len.data(), C.h_off.data());
+    });
+    C.h_off[nv] = C.total;
+    C.phase("host lengths + offsets");
     uint64_t max_window_words = 0;
     uint32_t max_chunks = 1;   // the tag records are only as long as some window has chunks
     {
-        Chunks C;
+        Chunks chunks;
         size_t nf = 0;
         for (uint32_t b0 = 0, nbw; b0 < n; b0 += nbw) {
-            while (nf < flush_at.size() && flush_at[nf] <= b0) ++nf;
-            nbw = form_window(b0, C, nf < flush_at.size() ? flush_at[nf] : n);
-            max_window_words = std::max<uint64_t>(max_window_words, h_off[b0 + nbw] - h_off[b0]);
-            max_chunks = std::max(max_chunks, C.n);
+            while (nf < C.flush_at.size() && C.flush_at[nf] <= b0) ++nf;
+            nbw = form_window(C, b0, chunks, nf < C.flush_at.size() ? C.flush_at[nf] : n);
+            max_window_words = std::max<uint64_t>(max_window_words, C.h_off[b0 + nbw] - C.h_off[b0]);
+            max_chunks = std::max(max_chunks, chunks.n);
         }
-        if (!flush_at.empty())   // (the sweeps' windows start anywhere: no window holds more than the window_cap longest sequences)
-            max_window_words = std::max<uint64_t>(max_window_words, h_off[std::min(n, window_cap)]);
+        if (!C.flush_at.empty())   // (the sweeps' windows start anywhere: no window holds more than the window_cap longest sequences)
+            max_window_words = std::max<uint64_t>(max_window_words, C.h_off[std::min(n, window_cap)]);
     }
-    // The chunk volume adapts (cur_frac below), so later windows are not the ones of this scan: bound a window's words
+    // The chunk volume adapts (adapt_chunks), so later windows are not the ones of this scan: bound a window's words
     // independently of the partition -- no more than the window_cap longest sequences, no more than kMaxChunks
     // chunks of the largest volume (a chunk closes before it would exceed that, or holds one sequence).
-    if (chunking && flush_at.empty())
+    if (C.chunking && C.flush_at.empty())
         max_window_words = std::max<uint64_t>(max_window_words,
-            std::min<uint64_t>(h_off[std::min(n, window_cap)], (uint64_t)kMaxChunks * std::max<uint64_t>(chunk_words, max_len)));
-    PGX_REQUIRE(max_window_words < 0xFFFFFFF0ull, "window too large");
-    PGX_HIP(d_touched.alloc((max_window_words + 16) * sizeof(Deferred)));   // entries set aside by an append round
-    if (chunking && n > window_cap / 2) max_chunks = kMaxChunks;   // (smaller chunks later may need all of them)
-    uint32_t tag_stride = 1;   // first-open tags: one record of tag_stride >= max_chunks words per code
-    while (tag_stride < max_chunks) tag_stride *= 2;
-    PGX_HIP(d_first.alloc((size_t)tag_stride * n_codes * 4 + 16));
-    // ---- windows --------------------------------------------------------------------------
-    std::vector<uint32_t> rep_seq;            // representative index -> sorted sequence index
-    HostVec<int32_t> cluster_of(ctx, CL_HOST_CLUSTER_OF, n, -1);   // sorted sequence index -> cluster
-    HostVec<int32_t> iden_of(ctx, CL_HOST_IDEN_OF, n, -1);     // identical residues against the representative, -1 = is one
-    PGX_REQUIRE(cluster_of.ok() && iden_of.ok(), "out of host memory");
-    Pinned<Pair> hW(ctx, CL_PIN_W), hK(ctx, CL_PIN_K);
-    Pinned<unsigned long long> h_best(ctx, CL_PIN_BEST), h_rcvis(ctx, CL_PIN_RCVIS);
-    Pinned<uint32_t> h_cnt(ctx, CL_PIN_CNT), h_blk(ctx, CL_PIN_BLK), h_new(ctx, CL_PIN_NEW), h_list(ctx, CL_PIN_LIST),
-        h_push(ctx, CL_PIN_PUSH);
-    Pinned<Pair> h_gather(ctx, CL_PIN_GATHER);
-    constexpr uint32_t kPrefix = 65536;  // initial capacity (records) of the host copy of the window's pairs
-    PGX_HIP(h_best.reserve(window_cap)); PGX_HIP(h_cnt.reserve(C_COUNT)); PGX_HIP(h_blk.reserve(kBlockCap));
-    PGX_HIP(h_new.reserve(window_cap)); PGX_HIP(hK.reserve(pair_cap_k)); PGX_HIP(hW.reserve(kPrefix));
-    PGX_HIP(h_rcvis.reserve(window_cap)); PGX_HIP(h_push.reserve(2 * (size_t)window_cap + 4 * kBlockCap));
-    PGX_HIP(h_list.reserve(pair_cap_k)); PGX_HIP(h_gather.reserve(pair_cap_k));
-    // what a window's CLOSE publishes has its own host buffers, one set per window in flight
-    Pinned<Pair> hW2(ctx, CL_PIN_W2);
-    Pinned<unsigned long long> h_best2(ctx, CL_PIN_BEST2);
-    Pinned<uint32_t> h_ccnt(ctx, CL_PIN_CCNT), h_ccnt2(ctx, CL_PIN_CCNT2);
-    PGX_HIP(h_ccnt.reserve(C_COUNT));
-    if (overlap) { PGX_HIP(hW2.reserve(kPrefix)); PGX_HIP(h_best2.reserve(window_cap)); PGX_HIP(h_ccnt2.reserve(C_COUNT)); }
-    struct Events {   // (destroyed on every way out)
-        hipEvent_t strike[2] = {nullptr, nullptr}, post[2] = {nullptr, nullptr};
-        ~Events() { for (hipEvent_t e : strike) if (e) (void)hipEventDestroy(e); for (hipEvent_t e : post) if (e) (void)hipEventDestroy(e); }
-    } ev;
-    for (int i = 0; i < 2; ++i) {
-        PGX_HIP(hipEventCreateWithFlags(&ev.strike[i], hipEventDisableTiming));
-        PGX_HIP(hipEventCreateWithFlags(&ev.post[i], hipEventDisableTiming));
+            std::min<uint64_t>(C.h_off[std::min(n, window_cap)], (uint64_t)kMaxChunks * std::max<uint64_t>(C.chunk_words, max_len)));
+    CL_REQUIRE(max_window_words < 0xFFFFFFF0ull, "window too large");
+    C.max_window_words = max_window_words;
+    PGX_HIP(C.d_touched.alloc((max_window_words + 16) * sizeof(Deferred)));   // entries set aside by an append round
+    if (C.chunking && n > window_cap / 2) max_chunks = kMaxChunks;   // (smaller chunks later may need all of them)
+    while (C.tag_stride < max_chunks) C.tag_stride *= 2;   // first-open tags: one record of tag_stride >= max_chunks words per code
+    PGX_HIP(C.d_first.alloc((size_t)C.tag_stride * C.n_codes * 4 + 16));
+    C.cluster_of = HostVec<int32_t>(ctx, CL_HOST_CLUSTER_OF, n, -1);
+    C.iden_of = HostVec<int32_t>(ctx, CL_HOST_IDEN_OF, n, -1);
+    CL_REQUIRE(C.cluster_of.ok() && C.iden_of.ok(), "out of host memory");
+    WindowSet &s0 = C.sets[0], &s1 = C.sets[1];
+    PGX_HIP(s0.h_best.reserve(window_cap)); PGX_HIP(C.h_cnt.reserve(C_COUNT)); PGX_HIP(C.h_blk.reserve(kBlockCap));
+    PGX_HIP(C.h_new.reserve(window_cap)); PGX_HIP(C.hK.reserve(C.pair_cap_k)); PGX_HIP(s0.hW.reserve(kPrefix));
+    PGX_HIP(C.h_rcvis.reserve(window_cap)); PGX_HIP(C.h_push.reserve(2 * (size_t)window_cap + 4 * kBlockCap));
+    PGX_HIP(C.h_list.reserve(C.pair_cap_k)); PGX_HIP(C.h_gather.reserve(C.pair_cap_k));
+    PGX_HIP(s0.h_ccnt.reserve(C_COUNT));
+    if (C.overlap) { PGX_HIP(s1.hW.reserve(kPrefix)); PGX_HIP(s1.h_best.reserve(window_cap)); PGX_HIP(s1.h_ccnt.reserve(C_COUNT)); }
+    for (WindowSet &ws : C.sets) {
+        PGX_HIP(hipEventCreateWithFlags(&ws.strike, hipEventDisableTiming));
+        PGX_HIP(hipEventCreateWithFlags(&ws.post, hipEventDisableTiming));
     }
-    const hipStream_t st_main = st;
-    uint32_t *const dc_set[2] = {d_counters.as<uint32_t>(), d_counters2.as<uint32_t>()};
-    unsigned long long *d_rcvis_p = d_rcvis.as<unsigned long long>();
-    // record-sharded mode (see pgx.h): this process filters and aligns the window members ql % shard_count ==
-    // shard_index; the window's best keys live in the caller's exchange buffer and are all-gathered after
-    // every evaluation
-    const uint32_t shard_count = P->shard_count > 0 ? (uint32_t)P->shard_count : 1u;
-    if (native_exchange) {   // the library's own exchange buffers, laid out as pgx.h asks of a caller's
-        PGX_HIP(d_xsend.alloc((size_t)PGX_EXCHANGE_SLOTS * PGX_EXCHANGE_WORDS * 8));
-        PGX_HIP(d_xrecv.alloc((size_t)PGX_EXCHANGE_SLOTS * shard_count * PGX_EXCHANGE_WORDS * 8));
+    if (C.native_exchange) {   // the library's own exchange buffers, laid out as pgx.h asks of a caller's
+        PGX_HIP(C.d_xsend.alloc((size_t)PGX_EXCHANGE_SLOTS * PGX_EXCHANGE_WORDS * 8));
+        PGX_HIP(C.d_xrecv.alloc((size_t)PGX_EXCHANGE_SLOTS * C.shard_count * PGX_EXCHANGE_WORDS * 8));
     }
-    unsigned long long *const x_send = native_exchange ? d_xsend.as<unsigned long long>() : static_cast<unsigned long long *>(P->exchange_send);
-    const unsigned long long *const x_recv = native_exchange ? d_xrecv.as<unsigned long long>() : static_cast<const unsigned long long *>(P->exchange_recv);
-    unsigned long long *d_best = exchanging ? x_send : d_best_own.as<unsigned long long>();
-    const uint32_t shard_index = P->shard_count > 0 ? (uint32_t)P->shard_index : 0u;
-    const bool count_replicated = shard_index == 0;  // work every process repeats is counted by the first one only
-    // test hook (tests/test_gpu_cluster_sharded.py): PGX_INJECT_ERROR="<rank>:<n>" makes that process report a pair
-    // buffer overflow with its n-th exchange, to check that every process then leaves at the same point
-    int inject_rank = -1;
-    uint64_t inject_at = 0, n_exchanges = 0;
-    if (const char *e = std::getenv("PGX_INJECT_ERROR")) { unsigned long long at = 0; if (sscanf(e, "%d:%llu", &inject_rank, &at) == 2) inject_at = at; else inject_rank = -1; }
-    uint64_t visits_rc = 0;
-    unsigned long long *const d_best_set[2] = {d_best, exchanging ? d_best + PGX_EXCHANGE_WORDS : d_best2.as<unsigned long long>()};
-    uint8_t *const d_flags_set[2] = {d_flags.as<uint8_t>(), d_flags2.as<uint8_t>()};
-    std::vector<uint8_t> status(window_cap);
-    HostVec<uint8_t> strand_of(ctx, CL_HOST_STRAND_OF, n, (uint8_t)0);
-    PGX_REQUIRE(strand_of.ok(), "out of host memory");
-    std::vector<unsigned long long> winner_key(window_cap);  // strand<<63 | minc<<32 | sequence index of the winner
-    std::vector<uint32_t> new_reps, order_k, rank_of(window_cap), bucket_k(kBlockCap + 2), fill_k(kBlockCap + 2), flight;
-    auto real = [&](uint32_t k) { return k >= n ? k - n : k; };
-    auto pair_key = [&](const Pair &pp) {
-        return ((unsigned long long)(pp.q >= n) << 63) | ((unsigned long long)pp.minc << 32) | pp.r;
-    };
-    uint64_t n_rounds = 0;
-
-    uint64_t gpu_pairs = 0, gpu_aligned = 0, gpu_aligned_bytes = 0, filter_walk_words = 0;  // actual device work (reserved stats slots)
-    auto account = [&](const Pair *pp, uint32_t cnt) {
-        for (uint32_t i = 0; i < cnt; ++i) {
-            ++gpu_pairs;
-            if ((pp[i].flags & (F_DIAG_PASS | F_BAND_OK)) != (F_DIAG_PASS | F_BAND_OK)) continue;
-            ++gpu_aligned;
-            gpu_aligned_bytes += h_len[pp[i].q] + h_len[pp[i].r];
-        }
-    };
-    auto window_error = [&](uint32_t e, uint32_t at) {   // (the word is the OR over all processes in the record-sharded mode)
-        pgx_set_error("pgx_cluster_greedy: capacity failure in the window at %u%s:%s%s%s%s%s%s", at,
-                      exchanging ? " (on this or another process)" : "",
-                      e & E_TOUCHED ? " append scratch list full;" : "", e & E_POOL ? " overflow pool of the word index full;" : "",
-                      e & E_TABLE ? " exact table of the filter overflowed;" : "",
-                      e & E_BAND ? " alignment band wider than 64 diagonals;" : "", e & E_PAIRS ? " candidate pair buffer overflow;" : "",
-                      e & E_WORDMULT ? " a word occurs more than 65535 times in one sequence;" : "");
-    };
-    const bool trace = std::getenv("PGX_TRACE") != nullptr;
-    const uint32_t filter_grid = 4096u;
-    uint32_t epoch_idx = 0;      // append rounds of the index (line.epoch); 0 = never
-    uint32_t epoch_tag = 0;      // discovery rounds (first-open tags, 16 bits)
-    PGX_HIP(hipMemsetAsync(d_first.p, 0, (size_t)tag_stride * n_codes * 4, st));
-    phase("window set-up");
-    const auto t_loop0 = std::chrono::steady_clock::now();
-    double t_resolve = 0.0, t_close = 0.0;
-    uint64_t n_blocks = 0;
-    g_wait_s = 0.0;
-    std::function<int()> deferred;  // bookkeeping of the window before, see the close of a window
-    std::vector<uint32_t> members;  // cluster -> members numbered so far
-    uint64_t pending_words = 0;     // ... and its words
-    Chunks chunks;
+    C.x_send = C.native_exchange ? C.d_xsend.as<unsigned long long>() : static_cast<unsigned long long *>(P->exchange_send);
+    C.x_recv = C.native_exchange ? C.d_xrecv.as<unsigned long long>() : static_cast<const unsigned long long *>(P->exchange_recv);
+    for (int s = 0; s < (C.overlap ? 2 : 1); ++s) {   // the sets' device pointers
+        WindowSet &ws = C.sets[s];
+        ws.d_best = C.exchanging ? C.x_send + (size_t)s * PGX_EXCHANGE_WORDS : ws.best_buf.as<unsigned long long>();
+        ws.d_done = ws.flags_buf.as<uint8_t>(); ws.d_inblk = ws.d_done + window_cap;
+        ws.d_hascand = ws.d_done + 2 * (size_t)window_cap; ws.d_accepted = ws.d_done + 3 * (size_t)window_cap;
+        ws.pairsW = ws.pairs_buf.as<Pair>();
+        ws.d_gs = ws.gscratch_buf.as<uint32_t>();
+    }
+    if (const char *e = std::getenv("PGX_INJECT_ERROR")) { unsigned long long at = 0; if (sscanf(e, "%d:%llu", &C.inject_rank, &at) == 2) C.inject_at = at; else C.inject_rank = -1; }
+    C.status.resize(window_cap);
+    C.strand_of = HostVec<uint8_t>(ctx, CL_HOST_STRAND_OF, n, (uint8_t)0);
+    CL_REQUIRE(C.strand_of.ok(), "out of host memory");
+    C.winner_key.resize(window_cap);
+    C.rank_of.resize(window_cap); C.bucket_k.resize(kBlockCap + 2); C.fill_k.resize(kBlockCap + 2);
+    PGX_HIP(hipMemsetAsync(C.d_first.p, 0, (size_t)C.tag_stride * C.n_codes * 4, C.st_main));
+    C.phase("window set-up");
     // Memory-chunked rule: at a flush position every sequence not yet placed is compared with the index as it is
     // (a SWEEP: windows over the rest of the list that run phase A only; a member with an accepted representative is
     // placed there and then, the others stay in the game), then the index is emptied and clustering goes on.
-    Pinned<uint8_t> h_taken(ctx, CL_PIN_TAKEN);   // per sorted sequence: placed by a sweep (the device reads it through the mapping)
-    if (!flush_at.empty()) { PGX_HIP(h_taken.reserve(n)); std::fill(h_taken.p, h_taken.p + n, (uint8_t)0); }
-    auto drain = [&]() -> int {     // nothing in flight, no bookkeeping pending
-        if (deferred) { int rc = deferred(); deferred = nullptr; if (rc) return rc; }
-        PGX_HIP(hipStreamSynchronize(st_main));
-        PGX_HIP(hipStreamSynchronize(ctx->stream2));
-        return PGX_OK;
-    };
-    size_t next_flush = 0;
-    bool sweeping = false;
-    uint32_t sweep_at = 0;
-    for (uint32_t cursor = 0, nb = 0; cursor < n;) {
-        if (!sweeping && next_flush < flush_at.size() && cursor == flush_at[next_flush]) {
-            ++next_flush;
-            sweeping = true; sweep_at = cursor;
-            int rc = drain(); if (rc) return rc;
-        }
-        const bool sweep = sweeping;
-        const uint32_t b0 = sweep ? sweep_at : cursor;
-        nb = form_window(b0, chunks, sweep || next_flush >= flush_at.size() ? n : flush_at[next_flush]);   // queries of this window
-        // this window's own state and stream (see `overlap`); the names below shadow the first set's
-        const int set = overlap ? (int)(S.sweeps & 1u) : 0;
-        const hipStream_t st = set ? ctx->stream2 : st_main;
-        uint32_t *const dc = dc_set[set];
-        unsigned long long *const d_best = d_best_set[set];
-        uint8_t *const d_done = d_flags_set[set], *const d_inblk = d_done + window_cap;
-        uint8_t *const d_hascand = d_done + 2 * (size_t)window_cap, *const d_accepted = d_done + 3 * (size_t)window_cap;
-        Pinned<Pair> &hW_w = set ? hW2 : hW;
-        Pinned<unsigned long long> &h_best_w = set ? h_best2 : h_best;
-        Pinned<uint32_t> &h_ccnt_w = set ? h_ccnt2 : h_ccnt;
-        uint32_t *const d_gs = (set ? d_gscratch2 : d_gscratch).as<uint32_t>();
-        if (overlap && S.sweeps > 0)   // the index of the window before is final (its last strike-out is done)
-            PGX_HIP(hipStreamWaitEvent(st, ev.strike[set ^ 1], 0));
-        bool strike_recorded = false;
-        const uint32_t ns = both ? 2 * nb : nb;            // window slots: + one per reverse complement
-        const uint32_t n_reps = (uint32_t)rep_seq.size();
-        const uint64_t window_words = h_off[b0 + nb] - h_off[b0];
-        // (the bookkeeping of the window before may still be pending: its members count as representatives)
-        { int rc = ensure_pool(S.rep_words + pending_words + window_words, st); if (rc) return rc; }
-        uint32_t *d_poolp = d_pool[pool_cur].as<uint32_t>();
-        if (nt) {  // at cd-hit-est's -n 5 -c 0.8 one shared word is enough: size the pair buffer for all pairs
-            const uint64_t need = (uint64_t)ns * ((uint64_t)n_reps + nb) + 1024;
-            if (need > (400ull << 20)) {
-                pgx_set_error("pgx_cluster_greedy: %llu candidate pairs in one window exceed the supported maximum",
-                              (unsigned long long)need);
-                return PGX_ERR_CAPACITY;
-            }
-            if (need > pair_cap) {
-                PGX_HIP(spin_sync(st));
-                if (deferred) { int rc = deferred(); deferred = nullptr; if (rc) return rc; }
-                pair_cap = (uint32_t)(need + need / 2);
-                PGX_HIP(d_pairsW.alloc((size_t)pair_cap * sizeof(Pair)));
-            }
-        }
-        S.sweeps++;
-        const auto t_sweep0 = std::chrono::steady_clock::now();
-        const uint64_t blocks_before = n_blocks;
-        // the general (int64, one pair per wave) aligner is only needed when some pair of this
-        // window cannot use the 16-lane fast path: query length + longest sequence, or the band
-        // LDS slot per pair of the 16-lane aligner: sized for two sequences as long as the window's longest query
-        const int two_len = 2 * (int)h_len[b0];
-        const int a16_slot = two_len <= 1024 - 96 ? 1024 : (two_len <= 1536 - 96 ? 1536 : (two_len <= 2048 - 96 ? 2048 : (two_len <= 3072 - 96 ? 3072 : kA16MaxSlot)));
-        Pair *pairsW = (set ? d_pairsW2 : d_pairsW).as<Pair>();
-        FilterArgs FA{};
-        FA.lines = d_lines.as<IndexLine>(); FA.pool = d_poolp; FA.newbits = d_newbits.as<uint32_t>();
-        FA.d_round_lo = dc + C_SEG0; FA.d_round_hi = dc + C_NEW; FA.epoch = 0;
-        FA.b0 = b0; FA.nbq = nb; FA.ns = ns; FA.shard_index = shard_index; FA.shard_count = shard_count;
-        FA.req_aan = d_aan.as<int32_t>(); FA.best = d_best; FA.done = d_done;
-        FA.pairs = pairsW; FA.n_pairs = dc + C_NW; FA.pair_cap = pair_cap;
-        FA.visits = d_visits.as<unsigned long long>(); FA.rc_visits = d_rcvis_p; FA.err = dc + C_ERR;
-        FA.qlist = nullptr; FA.d_nq = nullptr; FA.mark = nullptr; FA.count_visits = 1u;
-        FA.lean = stats == nullptr && !std::getenv("PGX_NO_LEAN") ? 1u : 0u;
+    if (!C.flush_at.empty()) { PGX_HIP(C.h_taken.reserve(n)); std::fill(C.h_taken.p, C.h_taken.p + n, (uint8_t)0); }
+    return PGX_OK;
+}
 
-        window_init_kernel<<<(window_cap + 255) / 256, 256, 0, st>>>(dc, d_best, both ? d_rcvis_p : nullptr, d_done, window_cap);
-        if (!flush_at.empty() && next_flush > 0)
-            mark_absent_kernel<<<(nb + 255) / 256, 256, 0, st>>>(h_taken.p + b0, nb, d_done, d_best);
-        LAUNCH_CHECK();
-        // the host side of a window starts with the bookkeeping of the window before (deferred behind this window's
-        // first kernels), then the member states
-        auto begin_host_side = [&]() -> int {
-            if (deferred) { int rc = deferred(); deferred = nullptr; if (rc) return rc; }
-            for (uint32_t q = 0; q < nb; ++q) status[q] = cluster_of[b0 + q] >= 0 ? ST_ABSENT : ST_OPEN;
-            return PGX_OK;
-        };
-        // Can a pair of the evaluation at hand fall outside the 16-lane aligner's slots? Its band cannot when the band
-        // width is at most 32; its lengths can when the candidates are OLDER representatives (the pass over the whole
-        // index: any length) or when the window's own longest pair exceeds the largest slot. Every other evaluation
-        // pairs members of this window with each other -- two sequences no longer than the window's first, which is
-        // what the slot was sized for -- and does not launch the general aligner at all (an empty launch is ≈ 11 us of
-        // stream time, 105 of them per step on cfg-3s).
-        bool older_reps = false;
-        // diag + align of a selection of pair records, enqueued on the stream
-        auto evaluate = [&](Pair *pairs, const PairSel &sel, unsigned long long *best_arr, uint32_t grid_hint) -> int {
-            const uint32_t dg = grid_hint ? std::min(diag_grid, grid_hint) : diag_grid;
-            const uint32_t ag = grid_hint ? std::min(align_grid, (grid_hint + 15) / 16) : align_grid;
-            {
-                ProfScope prof(ctx, "diag_kernel", st);
-                // (LDS by the window's longest query: 512 positions give six waves per SIMD, 1024 four, 2048 two and a half)
-                auto kern = h_len[b0] > packed_len ? diag_kernel<64, unsigned long long>
-                            : (h_len[b0] <= kDiagLdsSmall ? diag_kernel<kDiagLdsSmall, uint32_t>
-                               : (h_len[b0] <= 2 * kDiagLdsSmall ? diag_kernel<2 * kDiagLdsSmall, uint32_t> : diag_kernel<kDiagLdsCap, uint32_t>));
-                kern<<<dg, 64, 0, st>>>(DS, nullptr, pairs, sel, d_aa1.as<int32_t>(), d_aas.as<int32_t>(),
-                                        P->band_width, P->identity, d_gs, gs_stride, gs_cells, dc + C_WIDE, dc + C_ERR);
-            }
-            LAUNCH_CHECK();
-            {
-                ProfScope prof(ctx, "align_kernel", st);
-                auto kern = a16_slot == 1024 ? align16_kernel<1024> : (a16_slot == 1536 ? align16_kernel<1536> : (a16_slot == 2048 ? align16_kernel<2048>
-                            : (a16_slot == 3072 ? align16_kernel<3072> : align16_kernel<kA16MaxSlot>)));
-                kern<<<ag, 256, 0, st>>>(DS, nullptr, pairs, sel, d_aa1.as<int32_t>(), P->identity, b0, best_arr, 0u, dc + C_WIDE, 0u);
-                // a window whose longest query does not fit the 4 KB slots twice over: the pairs left get 8 KB slots (the
-                // general aligner computes a cell per lane every OTHER step, one pair per wave: 1.6 ms for the first
-                // window of cfg-3s, whose longest sequences are 2,101 residues)
-                const bool big_pass = a16_slot == kA16MaxSlot && two_len > kA16MaxSlot - 96;
-                const bool may_be_wide = older_reps || two_len > a16_slot - 96 || P->band_width > 32;
-                if (big_pass)
-                    align16_kernel<kA16BigSlot><<<ag, 256, 0, st>>>(DS, nullptr, pairs, sel, d_aa1.as<int32_t>(), P->identity, b0, best_arr,
-                                                                    0u, dc + C_WIDE, 1u);
-                if (may_be_wide)
-                    align_kernel<<<grid_hint ? std::min(align_grid, (grid_hint + 3) / 4) : align_grid, 256, 0, st>>>(
-                        DS, nullptr, pairs, sel, d_aa1.as<int32_t>(), P->identity, b0, best_arr, 0u, 1, (big_pass ? kA16BigSlot : a16_slot) - 96, dc + C_WIDE);
-            }
-            LAUNCH_CHECK();
-            return PGX_OK;
-        };
-        // record-sharded mode: every process learns every member's best key (one all-gather per evaluation,
-        // enqueued on the stream by the caller's collective library; no host synchronisation)
-        auto exchange_best = [&]() -> int {
-            if (!exchanging) return PGX_OK;
-            ++n_exchanges;
-            exchange_prepare_kernel<<<1, 1, 0, st>>>(dc, pair_cap, d_best,
-                                                     inject_rank == (int)shard_index && inject_at == n_exchanges ? (uint32_t)E_PAIRS : 0u);
-            if (native_exchange) {
-                const int rc = pgx_rccl_all_gather_u64(ctx, x_send + (size_t)set * PGX_EXCHANGE_WORDS,
-                                                       const_cast<unsigned long long *>(x_recv) + (size_t)set * shard_count * PGX_EXCHANGE_WORDS,
-                                                       PGX_EXCHANGE_WORDS, st);
-                if (rc) return rc;
-            } else if (P->exchange(P->exchange_user, (void *)st, set) != 0) {
-                pgx_set_error("pgx_cluster_greedy: the exchange callback failed in the window at %u", b0);
-                return PGX_ERR_INTERNAL;
-            }
-            min_rows_kernel<<<(nb + 255) / 256, 256, 0, st>>>(
-                x_recv + (size_t)set * shard_count * PGX_EXCHANGE_WORDS,
-                shard_count, PGX_EXCHANGE_WORDS, nb, d_best, dc + C_ERR);
-            LAUNCH_CHECK();
-            return PGX_OK;
-        };
-        // the window's pairs found since the last round_begin: evaluated, winners folded into best[]
-        auto evaluate_round = [&]() -> int {
-            const PairSel sel{dc + C_EVAL0, dc + C_NW, pair_cap, nullptr, 0, nullptr, nullptr, nullptr, b0, 0, 0};
-            int rc = evaluate(pairsW, sel, d_best, 0);
-            if (rc) return rc;
-            return exchange_best();
-        };
-        // phase A: against the representatives that exist already
-        if (b0 > 0) {
-            {
-                ProfScope prof(ctx, "filter_kernel<all>", st);
-                auto kern = nt ? filter_kernel<true, false> : filter_kernel<false, false>;
-                kern<<<std::min(filter_grid, (ns + 3) / 4), 256, 0, st>>>(DS, FA);
-            }
-            LAUNCH_CHECK();
-            filter_walk_words += window_words * (both ? 2 : 1) / shard_count;
-            older_reps = true;
-            int rc = evaluate_round();
-            older_reps = false;
-            if (rc) return rc;
+// The window's stream waits for the index of the window before; pool and (nucleotides) pair buffer are sized; the
+// window's geometry and base FilterArgs are computed; its counters, best keys and flags are reset on the device.
+int open_window(ClusterCall &C, WindowSet &ws, Window &W) {
+    const uint32_t b0 = W.b0, nb = W.nb;
+    if (C.overlap && C.S.sweeps > 0)   // the index of the window before is final (its last strike-out is done)
+        PGX_HIP(hipStreamWaitEvent(ws.st, C.sets[W.set ^ 1].strike, 0));
+    W.ns = C.both ? 2 * nb : nb;
+    W.n_reps = (uint32_t)C.rep_seq.size();
+    W.window_words = C.h_off[b0 + nb] - C.h_off[b0];
+    // (the bookkeeping of the window before may still be pending: its members count as representatives)
+    { int rc = ensure_pool(C, C.S.rep_words + C.pending_words + W.window_words, ws.st); if (rc) return rc; }
+    W.d_poolp = C.d_pool[C.pool_cur].as<uint32_t>();
+    if (C.nt) {  // at cd-hit-est's -n 5 -c 0.8 one shared word is enough: size the pair buffer for all pairs
+        const uint64_t need = (uint64_t)W.ns * ((uint64_t)W.n_reps + nb) + 1024;
+        if (need > (400ull << 20)) {
+            pgx_set_error("pgx_cluster_greedy: %llu candidate pairs in one window exceed the supported maximum",
+                          (unsigned long long)need);
+            return PGX_ERR_CAPACITY;
         }
-        // append list[*lo, *hi) to the index as round `epoch_idx` (the bit map of touched codes is the round's)
-        auto index_append = [&](const uint32_t *list, const uint32_t *d_lo, const uint32_t *d_hi) -> int {
-            ++epoch_idx;
-            uint32_t *const map = d_newbits.as<uint32_t>() + (size_t)(epoch_idx & 1u) * bm_words;   // (clear: index_place_kernel of the round before)
-            uint32_t *const next_map = d_newbits.as<uint32_t>() + (size_t)((epoch_idx + 1u) & 1u) * bm_words;
-            ProfScope prof(ctx, "index_append", st);
-            index_append_kernel<<<512, 256, 0, st>>>(DS, list, d_lo, d_hi, d_lines.as<IndexLine>(), epoch_idx,
-                                                     map, b0, nb, d_touched.as<Deferred>(),
-                                                     dc + C_TOUCH, (uint32_t)max_window_words, dc + C_ERR);
-            index_grow_kernel<<<256, 256, 0, st>>>(d_lines.as<IndexLine>(), d_poolp, d_idx.as<uint32_t>(),
-                                                   (uint32_t)pool_cap, d_touched.as<Deferred>(), dc + C_TOUCH,
-                                                   (uint32_t)max_window_words, dc + C_ERR);
-            index_place_kernel<<<256, 256, 0, st>>>(d_lines.as<IndexLine>(), d_poolp, d_touched.as<Deferred>(),
-                                                    dc + C_TOUCH, (uint32_t)max_window_words, reinterpret_cast<uint4 *>(next_map),
-                                                    bm_words / 4);
-            LAUNCH_CHECK();
-            return PGX_OK;
-        };
-        // every window member against the entries round `epoch_idx` added (the representatives list[*lo, *hi))
-        auto filter_new_and_evaluate = [&](const uint32_t *d_lo, const uint32_t *d_hi) -> int {
-            FilterArgs F = FA;
-            F.epoch = epoch_idx; F.d_round_lo = d_lo; F.d_round_hi = d_hi;
-            F.newbits = d_newbits.as<uint32_t>() + (size_t)(epoch_idx & 1u) * bm_words;
-            {
-                ProfScope prof(ctx, "filter_kernel<new>", st);
-                auto kern = nt ? filter_kernel<true, true> : filter_kernel<false, true>;
-                kern<<<std::min(filter_grid, (ns + 3) / 4), 256, 0, st>>>(DS, F);
-            }
-            LAUNCH_CHECK();
-            filter_walk_words += window_words * (both ? 2 : 1) / shard_count;
-            return evaluate_round();
-        };
-        // Discovery rounds: still-open members that cannot have an earlier open candidate are certain new
-        // representatives (first_open_kernel / certain_kernel). They are confirmed at once, appended to the
-        // index, and the pass against them assigns most of the remaining members; a second round confirms
-        // the members the first round's representatives rejected (the outliers of their families). All on
-        // the device: the host learns the outcome with the first block's results.
-        uint32_t n_listed = 0;
-        if (sweep) { int rc = begin_host_side(); if (rc) return rc; }
-        if (!sweep) {   // ---- discovery rounds and blocks (a sweep window has neither: nothing is appended) ----
-        if (overlap && S.sweeps > 1)   // from here on the index is written: the window before must have closed
-            PGX_HIP(hipStreamWaitEvent(st, ev.post[set ^ 1], 0));
-        static const int n_disc = std::getenv("PGX_ROUNDS") ? std::atoi(std::getenv("PGX_ROUNDS")) : kDiscoveryRounds;
-        for (int round = 0; round < n_disc; ++round) {
-            if (++epoch_tag == 0xFFFFu) { PGX_HIP(hipMemsetAsync(d_first.p, 0, (size_t)tag_stride * n_codes * 4, st)); epoch_tag = 1; }
-            const uint32_t which = (uint32_t)round & 1u;
-            uint32_t *const d_n_open = dc + (which ? C_ROUND_OPEN2 : C_ROUND_OPEN);
-            list_open_kernel<<<(nb + 255) / 256, 256, 0, st>>>(d_best, d_done, b0, nb, d_ulist.as<uint32_t>(), dc, which);
-            LAUNCH_CHECK();
-            {
-                ProfScope prof(ctx, "discover_kernels", st);
-                first_open_kernel<<<std::min(2048u, (nb + 3) / 4), 256, 0, st>>>(DS, d_ulist.as<uint32_t>(), d_n_open, b0,
-                                                                                 epoch_tag, d_first.as<uint32_t>(), tag_stride,
-                                                                                 chunks, d_aan.as<int32_t>(), d_accepted);
-                certain_kernel<<<std::min(2048u, (nb + 3) / 4), 256, 0, st>>>(DS, d_ulist.as<uint32_t>(), d_n_open, b0,
-                                                                              both ? 1u : 0u, epoch_tag, d_first.as<uint32_t>(), tag_stride,
-                                                                              chunks,
-                                                                              d_aan.as<int32_t>(), d_accepted, d_done, d_new_list.as<uint32_t>(),
-                                                                              dc + C_NEW);
-            }
-            LAUNCH_CHECK();
-            int rc = index_append(d_new_list.as<uint32_t>(), dc + C_SEG0, dc + C_NEW);
-            if (rc) return rc;
-            rc = filter_new_and_evaluate(dc + C_SEG0, dc + C_NEW);
-            if (rc) return rc;
-        }
-        // Blocks: members still without a representative, <= block_cap at a time, in order. A block is
-        // resolved exactly: its members are appended to the index TENTATIVELY, as if all were
-        // representatives, so the filter finds the block's internal candidate pairs like any others;
-        // they are evaluated, the host walks the block in order, the entries of the members that joined a
-        // representative are struck out again, and every other window member is compared with what is
-        // left: the block's new representatives. Pair work stays close to what the one-by-one pass does.
-        bool first_block = true;
-        n_listed = 0;              // discovery representatives the host has seen
-        uint32_t n_struck = 0;     // members struck out of the index so far (offsets into the pinned list)
-        for (;;) {
-            select_block_kernel<<<1, kSelThreads, 0, st>>>(d_best, d_done, d_inblk, b0, nb, block_cap,
-                                                           d_blk_list.as<uint32_t>(), dc + C_BLK, dc + C_NK,
-                                                           d_hascand, window_cap, dc);  // + has_cand, accepted = 0
-            LAUNCH_CHECK();
-            {
-                int rc = index_append(d_blk_list.as<uint32_t>(), dc + C_ZERO, dc + C_BLK);
-                if (rc) return rc;
-                FilterArgs F = FA;   // the block's members against the block's (tentative) entries
-                F.epoch = epoch_idx; F.d_round_lo = dc + C_ZERO; F.d_round_hi = dc + C_BLK;
-                F.newbits = d_newbits.as<uint32_t>() + (size_t)(epoch_idx & 1u) * bm_words;
-                F.qlist = d_blk_list.as<uint32_t>(); F.d_nq = dc + C_BLK; F.mark = d_hascand; F.count_visits = 0u;
-                F.pairs = d_pairsK.as<Pair>(); F.n_pairs = dc + C_NK; F.pair_cap = pair_cap_k;
-                F.shard_count = 1; F.shard_index = 0;   // (replicated on every process)
-                ProfScope prof(ctx, "filter_kernel<block>", st);
-                auto kern = nt ? filter_kernel<true, true> : filter_kernel<false, true>;
-                kern<<<std::min(filter_grid, (block_cap * (both ? 2u : 1u) + 3) / 4), 256, 0, st>>>(DS, F);
-            }
-            LAUNCH_CHECK();
-            // A block member without an earlier in-block candidate (has_cand clear) is certainly a
-            // new representative; only pairs against those are evaluated up front. Second round on
-            // the device: a member that has candidates but was accepted by none of the certain
-            // representatives is LIKELY a representative itself (an outlier of its family), so the
-            // pairs against those follow. Whatever the in-order walk on the host still needs
-            // afterwards goes through follow-up rounds.
-            {
-                const PairSel selK{nullptr, dc + C_NK, pair_cap_k, nullptr, 0, nullptr, d_hascand, d_accepted, b0, 0, 2048};   // (a small block: all its pairs at once, the second round then finds nothing left)
-                int rc = evaluate(d_pairsK.as<Pair>(), selK, nullptr, 0);
-                if (rc) return rc;
-                const PairSel selK2{nullptr, dc + C_NK, pair_cap_k, nullptr, 0, d_hascand, d_accepted, nullptr, b0, 1, 0};
-                rc = evaluate(d_pairsK.as<Pair>(), selK2, nullptr, 0);
-                if (rc) return rc;
-            }
-            // one round trip: counters, the block list, the in-block pairs (and the representatives the
-            // discovery rounds confirmed), written to host memory by one kernel
-            {
-                PubArgs pa{};
-                pa.seg[0] = {dc, h_cnt.p, nullptr, C_COUNT, 1, C_COUNT};
-                pa.seg[1] = {d_blk_list.as<uint32_t>(), h_blk.p, dc + C_BLK, 0, 1, block_cap};
-                pa.seg[2] = {d_pairsK.as<uint32_t>(), reinterpret_cast<uint32_t *>(hK.p), dc + C_NK, 0, kPairWords, pair_cap_k};
-                pa.n = 3;
-                if (first_block) pa.seg[pa.n++] = {d_new_list.as<uint32_t>(), h_new.p, dc + C_NEW, 0, 1, window_cap};
-                publish_kernel<<<64, 256, 0, st>>>(pa);
-                LAUNCH_CHECK();
-            }
-            if (first_block) {
-                // everything up to here was enqueued without looking at results: the previous window's
-                // bookkeeping runs now, behind that work, and only then is the member state reset
-                int rc = begin_host_side(); if (rc) return rc;
-            }
-            PGX_HIP(spin_sync(st));
-            if (h_cnt.p[C_ERR]) { window_error(h_cnt.p[C_ERR], b0); return PGX_ERR_CAPACITY; }
-            if (first_block) {
-                n_listed = h_cnt.p[C_NEW];
-                for (uint32_t i = 0; i < n_listed; ++i) status[h_new.p[i] - b0] = ST_REP;
-                first_block = false;
-            }
-            const uint32_t n_blk = h_cnt.p[C_BLK], n_open = h_cnt.p[C_OPEN], nK = h_cnt.p[C_NK];
-            if (h_cnt.p[C_NW] > pair_cap) {
-                pgx_set_error("pgx_cluster_greedy: candidate pair buffer overflow (%u) in the window at %u", h_cnt.p[C_NW], b0);
-                return PGX_ERR_CAPACITY;
-            }
-            if (nK > pair_cap_k) {
-                // more in-block candidate pairs than the buffer holds: give the block up (all its tentative
-                // entries are struck out again) and come back with a quarter of the members
-                if (block_cap <= kBlockCapMin) {
-                    pgx_set_error("pgx_cluster_greedy: block pair buffer overflow (%u) in the window at %u", nK, b0);
-                    return PGX_ERR_CAPACITY;
-                }
-                uint32_t *list = h_push.p + n_struck;
-                std::copy(h_blk.p, h_blk.p + n_blk, list);
-                n_struck += n_blk;
-                index_strike_kernel<<<std::min(1024u, (n_blk + 3) / 4), 256, 0, st>>>(DS, list, n_blk, d_lines.as<IndexLine>(), d_poolp);
-                retire_block_kernel<<<(nb + 255) / 256, 256, 0, st>>>(d_done, d_inblk, nb, 0u, nullptr);
-                LAUNCH_CHECK();
-                block_cap = std::max(kBlockCapMin, block_cap / 4);
-                continue;
-            }
-            if (n_blk == 0) {
-                if (overlap) { PGX_HIP(hipEventRecord(ev.strike[set], st)); strike_recorded = true; }   // nothing tentative is left
-                break;
-            }
-            // resolve the block in order: first accepted in-block representative by (minc, index)
-            const auto t_r0 = std::chrono::steady_clock::now();
-            ++n_blocks;
-            // bucket the in-block pairs by query (counting sort on the query's rank in the block)
-            for (uint32_t t = 0; t < n_blk; ++t) { rank_of[h_blk.p[t] - b0] = t; bucket_k[t] = 0; }
-            bucket_k[n_blk] = 0;
-            for (uint32_t i = 0; i < nK; ++i) bucket_k[rank_of[real(hK.p[i].q) - b0] + 1]++;
-            for (uint32_t t = 0; t < n_blk; ++t) bucket_k[t + 1] += bucket_k[t];   // bucket t = [bucket_k[t], bucket_k[t+1])
-            for (uint32_t t = 0; t < n_blk; ++t) fill_k[t] = bucket_k[t];
-            order_k.resize(nK);
-            for (uint32_t i = 0; i < nK; ++i) order_k[fill_k[rank_of[real(hK.p[i].q) - b0]]++] = i;
-            // In-order walk. For member q the sequential rule takes the accepted representative
-            // with the smallest (minc, index) among its in-block candidates that ARE
-            // representatives. Pairs that neither device round evaluated and that could precede
-            // the winner are collected for ALL still-open members in one pass (candidates that
-            // are themselves undecided count as possible representatives) and evaluated in a
-            // follow-up round; the walk repeats until every member is decided.
-            uint32_t t_first = 0;
-            for (;;) {
-                flight.clear();
-                bool any_open = false;
-                for (uint32_t t = t_first; t < n_blk; ++t) {
-                    const uint32_t k = h_blk.p[t], q = k - b0;
-                    if (status[q] != ST_OPEN) continue;
-                    const uint32_t lo = bucket_k[t], hi = bucket_k[t + 1];
-                    unsigned long long win = kNoBest, open_acc = kNoBest;
-                    int32_t win_iden = 0;
-                    for (uint32_t e = lo; e < hi; ++e) {
-                        const Pair &pr = hK.p[order_k[e]];
-                        const uint8_t su = status[pr.r - b0];
-                        if (su == ST_MEMBER || !(pr.flags & F_EVAL)) continue;
-                        if ((pr.flags & F_TOO_BIG) && (pr.flags & F_DIAG_PASS)) {
-                            pgx_set_error("pgx_cluster_greedy: alignment band wider than %d diagonals", kMaxBand);
-                            return PGX_ERR_CAPACITY;
-                        }
-                        if (!(pr.flags & F_ACCEPT)) continue;
-                        const unsigned long long key = pair_key(pr);
-                        if (su == ST_REP) { if (key < win) { win = key; win_iden = pr.iden; } }
-                        else if (key < open_acc) open_acc = key;  // wins if that member turns out a representative
-                    }
-                    bool needs = false;
-                    for (uint32_t e = lo; e < hi; ++e) {
-                        const Pair &pr = hK.p[order_k[e]];
-                        if (status[pr.r - b0] == ST_MEMBER || (pr.flags & F_EVAL)) continue;
-                        if (pair_key(pr) < win) { flight.push_back(order_k[e]); needs = true; }
-                    }
-                    if (needs || open_acc < win) { any_open = true; continue; }
-                    if (win != kNoBest) {
-                        status[q] = ST_MEMBER;
-                        winner_key[q] = win; iden_of[k] = win_iden; strand_of[k] = (uint8_t)(win >> 63);
-                    } else {
-                        status[q] = ST_REP;
-                    }
-                }
-                if (!any_open) break;
-                while (t_first < n_blk && status[h_blk.p[t_first] - b0] != ST_OPEN) ++t_first;
-                if (flight.empty()) { pgx_set_error("pgx_cluster_greedy: block resolution made no progress"); return PGX_ERR_INTERNAL; }
-                // follow-up round: evaluate the listed pairs and fetch their records back
-                const uint32_t nl = (uint32_t)flight.size();
-                ++n_rounds;
-                std::copy(flight.begin(), flight.end(), h_list.p);
-                PGX_HIP(hipMemcpyAsync(d_list.p, h_list.p, (size_t)nl * 4, hipMemcpyHostToDevice, st));
-                {
-                    const PairSel selL{nullptr, nullptr, 0, d_list.as<uint32_t>(), nl, nullptr, nullptr, nullptr, b0, 0, 0};
-                    int rc = evaluate(d_pairsK.as<Pair>(), selL, nullptr, nl);
-                    if (rc) return rc;
-                }
-                gather_pairs_kernel<<<(nl + 255) / 256, 256, 0, st>>>(d_pairsK.as<Pair>(), d_list.as<uint32_t>(), nl,
-                                                                      d_gather.as<Pair>());
-                LAUNCH_CHECK();
-                PGX_HIP(hipMemcpyAsync(h_gather.p, d_gather.p, (size_t)nl * sizeof(Pair), hipMemcpyDeviceToHost, st));
-                PGX_HIP(spin_sync(st));
-                for (uint32_t w = 0; w < nl; ++w) hK.p[flight[w]] = h_gather.p[w];
-            }
-            // block decided: new representatives in order + the candidates the one-by-one pass examines
-            new_reps.clear();
-            for (uint32_t t = 0; t < n_blk; ++t) {
-                const uint32_t k = h_blk.p[t], q = k - b0;
-                if (status[q] == ST_REP) new_reps.push_back(k);
-                const unsigned long long win = status[q] == ST_MEMBER ? winner_key[q] : kNoBest;
-                for (uint32_t e = bucket_k[t]; e < bucket_k[t + 1]; ++e) {
-                    const Pair &pr = hK.p[order_k[e]];
-                    if (status[pr.r - b0] != ST_REP) continue;
-                    if (pair_key(pr) > win) continue;
-                    if (!count_replicated) continue;
-                    S.filter_pairs++;
-                    if ((pr.flags & (F_DIAG_PASS | F_BAND_OK)) == (F_DIAG_PASS | F_BAND_OK)) {
-                        S.aligned_pairs++;
-                        S.aligned_rep_len += h_len[pr.r];
-                        S.dp_cells += (uint64_t)h_len[k] * (uint64_t)(pr.band_right - pr.band_left + 1);
-                    }
-                }
-            }
-            if (count_replicated) account(hK.p, nK);
-            t_resolve += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_r0).count();
-            // the members that joined a representative leave the index again; every window member is then
-            // compared with the block's representatives (the block's own members only count their visits)
-            {
-                uint32_t *list = h_push.p + n_struck;   // read from page-locked host memory; every block has its own range
-                uint32_t n_out = 0;
-                for (uint32_t t = 0; t < n_blk; ++t)
-                    if (status[h_blk.p[t] - b0] != ST_REP) list[n_out++] = h_blk.p[t];
-                n_struck += n_out;
-                if (n_out)
-                    index_strike_kernel<<<std::min(1024u, (n_out + 3) / 4), 256, 0, st>>>(DS, list, n_out, d_lines.as<IndexLine>(), d_poolp);
-                retire_block_kernel<<<(nb + 255) / 256, 256, 0, st>>>(d_done, d_inblk, nb, 1u, dc);
-                LAUNCH_CHECK();
-                if (overlap && n_open == n_blk) {   // the last block: from here on this window only reads the index
-                    PGX_HIP(hipEventRecord(ev.strike[set], st));
-                    strike_recorded = true;
-                }
-                int rc = filter_new_and_evaluate(dc + C_ZERO, dc + C_BLK);
-                if (rc) return rc;
-            }
-            if (n_open == n_blk) break;  // that was the last block
-        }
-        }   // (!sweep)
-        if (chunking && !sweep) {   // the discovery chunks of the windows to come (see chunk_frac)
-            const uint64_t blk = n_blocks - blocks_before;
-            if (blk >= 3) cur_frac = std::max(0.1, cur_frac * 0.5);
-            else if (blk <= 1) cur_frac = std::min(chunk_frac, cur_frac * 1.5);
-            chunk_words = std::max<uint64_t>(16384, (uint64_t)(cur_frac * thr_frac * (double)n_codes));
-        }
-        // ---- close the window ---------------------------------------------------------------
-        {   // counters, winners, and exactly the pair records that exist, in one launch
-            PubArgs pa{};
-            pa.seg[0] = {dc, h_ccnt_w.p, nullptr, C_COUNT, 1, C_COUNT};
-            pa.seg[1] = {reinterpret_cast<const uint32_t *>(d_best), reinterpret_cast<uint32_t *>(h_best_w.p), nullptr, nb, 2, nb};
-            pa.seg[2] = {reinterpret_cast<const uint32_t *>(pairsW), reinterpret_cast<uint32_t *>(hW_w.p), dc + C_NW, 0, kPairWords,
-                         (uint32_t)std::min<size_t>(hW_w.cap, pair_cap)};
-            pa.n = 3;
-            if (both) pa.seg[pa.n++] = {reinterpret_cast<const uint32_t *>(d_rcvis_p), reinterpret_cast<uint32_t *>(h_rcvis.p), nullptr, nb, 2, nb};
-            if (overlap && !strike_recorded) PGX_HIP(hipEventRecord(ev.strike[set], st));
-            publish_kernel<<<64, 256, 0, st>>>(pa);
-            LAUNCH_CHECK();
-            if (overlap) PGX_HIP(hipEventRecord(ev.post[set], st));
-        }
-        // What the close published is looked at by the window's bookkeeping, which waits for it first: with
-        // overlapping windows that is when the next window's first kernels have been enqueued, without right here.
-        auto closed = [&, b0, st, pairsW, ev_post = ev.post[set], p_cnt = &h_ccnt_w, p_hW = &hW_w](uint32_t &nW) -> int {
-            if (overlap) {
-                const auto t0 = std::chrono::steady_clock::now();
-                hipError_t e;
-                while ((e = hipEventQuery(ev_post)) == hipErrorNotReady) {
-                }
-                g_wait_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-                PGX_HIP(e);
-            } else {
-                PGX_HIP(spin_sync(st));
-            }
-            nW = p_cnt->p[C_NW];
-            if (p_cnt->p[C_ERR]) { window_error(p_cnt->p[C_ERR], b0); return PGX_ERR_CAPACITY; }
-            if (nW > pair_cap) {
-                pgx_set_error("pgx_cluster_greedy: candidate pair buffer overflow (%u > %u) in the window at %u", nW, pair_cap, b0);
-                return PGX_ERR_CAPACITY;
-            }
-            if (nW > p_hW->cap) {  // the host buffer was too small: grow it and fetch again (the window's stream is idle by now)
-                PGX_HIP(p_hW->reserve(nW));  // (reserve keeps nothing: copy the whole range again)
-                PGX_HIP(hipMemcpyAsync(p_hW->p, pairsW, (size_t)nW * sizeof(Pair), hipMemcpyDeviceToHost, st));
-                PGX_HIP(spin_sync(st));
-            }
-            return PGX_OK;
-        };
-        uint32_t nW = 0;
-        if (!overlap) { int rc = closed(nW); if (rc) return rc; }
-        // The window's bookkeeping -- winners, numbering of the new representatives, identities, the candidates
-        // the one-by-one pass would have examined -- works on the host copies only: it is deferred until the
-        // next window's first kernels are enqueued (the device starts the next window right away).
-        const auto t_c0 = std::chrono::steady_clock::now();
-        {
-            pending_words = window_words;
-            deferred = [&, b0, nb, nW, sweep, closed, p_best = &h_best_w, p_hW = &hW_w]() mutable -> int {
-                if (overlap) { int rc = closed(nW); if (rc) return rc; }
-                const Pair *pW = p_hW->p;
-                pending_words = 0;
-                // members that were never in a block: their winner is the 64-bit minimum in best[]
-                for (uint32_t q = 0; q < nb; ++q) {
-                    if (status[q] != ST_OPEN) continue;
-                    const unsigned long long key = p_best->p[q];
-                    if (key == kNoBest) {
-                        if (sweep) { status[q] = ST_NONE; continue; }   // no representative in the table being dropped
-                        pgx_set_error("pgx_cluster_greedy: unresolved member after the last block"); return PGX_ERR_INTERNAL;
-                    }
-                    status[q] = ST_MEMBER;
-                    winner_key[q] = key;
-                    strand_of[b0 + q] = (uint8_t)(key >> 63);
-                    if (sweep) h_taken.p[b0 + q] = 1;
-                }
-                if (both)  // reverse-strand word walks happen only for queries the forward strand did not place
-                    for (uint32_t q = 0; q < nb; ++q)
-                        if (status[q] == ST_REP || status[q] == ST_NONE || (status[q] == ST_MEMBER && (winner_key[q] >> 63))) visits_rc += h_rcvis.p[q];
-                // new representatives are numbered in sequence order
-                for (uint32_t q = 0; q < nb; ++q)
-                    if (status[q] == ST_REP) {
-                        cluster_of[b0 + q] = (int32_t)rep_seq.size();
-                        rep_seq.push_back(b0 + q);
-                        S.sum_len_reps += h_len[b0 + q];
-                        S.rep_words += h_wcnt[b0 + q];
-                    }
-                for (uint32_t q = 0; q < nb; ++q)
-                    if (status[q] == ST_MEMBER) cluster_of[b0 + q] = cluster_of[(uint32_t)winner_key[q] & 0x7FFFFFFFu];
-                account(pW, nW);
-                bool fits = true;
-                for (uint32_t i = 0; i < nW; ++i) {
-                    const Pair &p = pW[i];
-                    const uint32_t k = real(p.q), q = k - b0;
-                    if ((p.flags & F_TOO_BIG) && (p.flags & F_DIAG_PASS)) { fits = false; continue; }
-                    const unsigned long long key = pair_key(p);
-                    // the one-by-one pass examines candidates in key order up to and including the winner
-                    if (status[q] == ST_REP || status[q] == ST_NONE || key <= winner_key[q]) {
-                        S.filter_pairs++;
-                        if ((p.flags & (F_DIAG_PASS | F_BAND_OK)) == (F_DIAG_PASS | F_BAND_OK)) {
-                            S.aligned_pairs++;
-                            S.aligned_rep_len += h_len[p.r];
-                            S.dp_cells += (uint64_t)h_len[k] * (uint64_t)(p.band_right - p.band_left + 1);
-                        }
-                        if ((p.flags & F_ACCEPT) && status[q] == ST_MEMBER && key == winner_key[q]) iden_of[k] = p.iden;
-                    }
-                }
-                if (!fits) {
-                    pgx_set_error("pgx_cluster_greedy: alignment band wider than %d diagonals", kMaxBand);
-                    return PGX_ERR_CAPACITY;
-                }
-                // the window's outputs, in the caller's order; member numbers follow the sorted order (A.3)
-                members.resize(rep_seq.size(), 0u);
-                for (uint32_t q = 0; q < nb; ++q) {
-                    if (status[q] == ST_ABSENT || status[q] == ST_NONE) continue;   // (written when placed / not placed yet)
-                    const uint32_t k = b0 + q, o = order[k];
-                    const int32_t c = cluster_of[k];
-                    out_cluster[o] = c;
-                    out_member[o] = (int32_t)members[(size_t)c]++;
-                    out_identity[o] = iden_of[k] >= 0 ? (float)iden_of[k] / (float)h_len[k] : 0.f;
-                    if (out_strand) out_strand[o] = strand_of[k];   // (set for members only)
-                }
-                return PGX_OK;
-            };
-        }
-        const bool trace2 = trace && std::getenv("PGX_TRACE")[0] == '2';
-        if (nt || trace2) {   // (nucleotide windows size their pair buffer from the number of representatives)
-            int rc = deferred(); deferred = nullptr; if (rc) return rc;
-        }
-        t_close += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_c0).count();
-        if (trace2)
-            fprintf(stderr, "[pgx] window %4llu b0 %8u nb %6u len %5u..%5u blocks %2llu reps +%5zu (discovery %5u) (total %7zu) pairs %7u  %.2f ms\n",
-                    (unsigned long long)S.sweeps, b0, nb, h_len[b0], h_len[b0 + nb - 1],
-                    (unsigned long long)(n_blocks - blocks_before), rep_seq.size() - n_reps, n_listed, rep_seq.size(), nW,
-                    1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t_sweep0).count());
-        if (!sweep) { cursor += nb; continue; }
-        sweep_at += nb;
-        if (sweep_at >= n) {   // the sweep is complete: the index is emptied, clustering goes on with what is left
-            int rc = drain(); if (rc) return rc;
-            PGX_HIP(hipMemsetAsync(d_lines.p, 0, (size_t)n_codes * sizeof(IndexLine), st_main));
-            const uint32_t one = 1u;
-            PGX_HIP(hipMemcpyAsync(d_idx.p, &one, 4, hipMemcpyHostToDevice, st_main));
-            PGX_HIP(hipStreamSynchronize(st_main));
-            sweeping = false;
+        if (need > C.pair_cap) {
+            PGX_HIP(spin_sync(ws.st));
+            { int rc = run_pending(C); if (rc) return rc; }
+            C.pair_cap = (uint32_t)(need + need / 2);
+            PGX_HIP(ws.pairs_buf.alloc((size_t)C.pair_cap * sizeof(Pair)));
+            ws.pairsW = ws.pairs_buf.as<Pair>();
         }
     }
-    if (deferred) { int rc = deferred(); deferred = nullptr; if (rc) return rc; }
-    if (trace)
-        fprintf(stderr, "[pgx] windows %llu blocks %llu (+%llu follow-up rounds): loop %.1f ms = wait %.1f + block resolve %.1f + window close %.1f + "
-                "enqueue/other %.1f\n", (unsigned long long)S.sweeps, (unsigned long long)n_blocks, (unsigned long long)n_rounds,
-                1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t_loop0).count(), 1e3 * g_wait_s,
-                1e3 * t_resolve, 1e3 * t_close,
-                1e3 * (std::chrono::duration<double>(std::chrono::steady_clock::now() - t_loop0).count() - g_wait_s -
-                       t_resolve - t_close));
+    C.S.sweeps++;
+    W.t_sweep0 = Clock::now();
+    W.blocks_before = C.n_blocks;
+    // the general (int64, one pair per wave) aligner is only needed when some pair of this
+    // window cannot use the 16-lane fast path: query length + longest sequence, or the band
+    W.two_len = 2 * (int)C.h_len[b0];
+    const int two_len = W.two_len;
+    W.a16_slot = two_len <= 1024 - 96 ? 1024 : (two_len <= 1536 - 96 ? 1536 : (two_len <= 2048 - 96 ? 2048 : (two_len <= 3072 - 96 ? 3072 : kA16MaxSlot)));
+    unsigned long long *const d_rcvis = C.d_rcvis.as<unsigned long long>();
+    FilterArgs &FA = W.FA;
+    FA.lines = C.d_lines.as<IndexLine>(); FA.pool = W.d_poolp; FA.newbits = C.d_newbits.as<uint32_t>();
+    FA.d_round_lo = ws.dc + C_SEG0; FA.d_round_hi = ws.dc + C_NEW; FA.epoch = 0;
+    FA.b0 = b0; FA.nbq = nb; FA.ns = W.ns; FA.shard_index = C.shard_index; FA.shard_count = C.shard_count;
+    FA.req_aan = C.d_aan.as<int32_t>(); FA.best = ws.d_best; FA.done = ws.d_done;
+    FA.pairs = ws.pairsW; FA.n_pairs = ws.dc + C_NW; FA.pair_cap = C.pair_cap;
+    FA.visits = C.d_visits.as<unsigned long long>(); FA.rc_visits = d_rcvis; FA.err = ws.dc + C_ERR;
+    FA.qlist = nullptr; FA.d_nq = nullptr; FA.mark = nullptr; FA.count_visits = 1u;
+    FA.lean = !C.want_stats && !std::getenv("PGX_NO_LEAN") ? 1u : 0u;
 
+    window_init_kernel<<<(C.window_cap + 255) / 256, 256, 0, ws.st>>>(ws.dc, ws.d_best, C.both ? d_rcvis : nullptr, ws.d_done, C.window_cap);
+    if (W.mark_absent)
+        mark_absent_kernel<<<(nb + 255) / 256, 256, 0, ws.st>>>(C.h_taken.p + b0, nb, ws.d_done, ws.d_best);
+    LAUNCH_CHECK();
+    return PGX_OK;
+}
+
+// phase A: against the representatives that exist already
+int phase_a(ClusterCall &C, WindowSet &ws, Window &W) {
+    {
+        ProfScope prof(C.ctx, "filter_kernel<all>", ws.st);
+        auto kern = C.nt ? filter_kernel<true, false> : filter_kernel<false, false>;
+        kern<<<std::min(kFilterGrid, (W.ns + 3) / 4), 256, 0, ws.st>>>(C.DS, W.FA);
+    }
+    LAUNCH_CHECK();
+    C.filter_walk_words += W.window_words * (C.both ? 2 : 1) / C.shard_count;
+    W.older_reps = true;
+    const int rc = evaluate_round(C, ws, W);
+    W.older_reps = false;
+    return rc;
+}
+
+// Discovery rounds: still-open members that cannot have an earlier open candidate are certain new
+// representatives (first_open_kernel / certain_kernel). They are confirmed at once, appended to the
+// index, and the pass against them assigns most of the remaining members; a second round confirms
+// the members the first round's representatives rejected (the outliers of their families). All on
+// the device: the host learns the outcome with the first block's results.
+int discovery_rounds(ClusterCall &C, WindowSet &ws, Window &W) {
+    const hipStream_t st = ws.st;
+    uint32_t *const dc = ws.dc;
+    const uint32_t b0 = W.b0, nb = W.nb;
+    if (C.overlap && C.S.sweeps > 1)   // from here on the index is written: the window before must have closed
+        PGX_HIP(hipStreamWaitEvent(st, C.sets[W.set ^ 1].post, 0));
+    static const int n_disc = std::getenv("PGX_ROUNDS") ? std::atoi(std::getenv("PGX_ROUNDS")) : kDiscoveryRounds;
+    for (int round = 0; round < n_disc; ++round) {
+        if (++C.epoch_tag == 0xFFFFu) { PGX_HIP(hipMemsetAsync(C.d_first.p, 0, (size_t)C.tag_stride * C.n_codes * 4, st)); C.epoch_tag = 1; }
+        const uint32_t which = (uint32_t)round & 1u;
+        uint32_t *const d_n_open = dc + (which ? C_ROUND_OPEN2 : C_ROUND_OPEN);
+        list_open_kernel<<<(nb + 255) / 256, 256, 0, st>>>(ws.d_best, ws.d_done, b0, nb, C.d_ulist.as<uint32_t>(), dc, which);
+        LAUNCH_CHECK();
+        {
+            ProfScope prof(C.ctx, "discover_kernels", st);
+            first_open_kernel<<<std::min(2048u, (nb + 3) / 4), 256, 0, st>>>(C.DS, C.d_ulist.as<uint32_t>(), d_n_open, b0,
+                                                                             C.epoch_tag, C.d_first.as<uint32_t>(), C.tag_stride,
+                                                                             W.chunks, C.d_aan.as<int32_t>(), ws.d_accepted);
+            certain_kernel<<<std::min(2048u, (nb + 3) / 4), 256, 0, st>>>(C.DS, C.d_ulist.as<uint32_t>(), d_n_open, b0,
+                                                                          C.both ? 1u : 0u, C.epoch_tag, C.d_first.as<uint32_t>(), C.tag_stride,
+                                                                          W.chunks,
+                                                                          C.d_aan.as<int32_t>(), ws.d_accepted, ws.d_done, C.d_new_list.as<uint32_t>(),
+                                                                          dc + C_NEW);
+        }
+        LAUNCH_CHECK();
+        int rc = index_append(C, ws, W, C.d_new_list.as<uint32_t>(), dc + C_SEG0, dc + C_NEW);
+        if (rc) return rc;
+        rc = filter_new_and_evaluate(C, ws, W, dc + C_SEG0, dc + C_NEW);
+        if (rc) return rc;
+    }
+    return PGX_OK;
+}
+
+// One block, enqueued without looking at results: the members are selected and appended to the index TENTATIVELY, as if
+// all were representatives, so the filter finds the block's internal candidate pairs like any others; two device
+// rounds evaluate the pairs most likely needed; one kernel writes counters, block list and pairs to host memory.
+int enqueue_block(ClusterCall &C, WindowSet &ws, Window &W, bool first_block) {
+    const hipStream_t st = ws.st;
+    uint32_t *const dc = ws.dc;
+    const uint32_t b0 = W.b0;
+    select_block_kernel<<<1, kSelThreads, 0, st>>>(ws.d_best, ws.d_done, ws.d_inblk, b0, W.nb, C.block_cap,
+                                                   C.d_blk_list.as<uint32_t>(), dc + C_BLK, dc + C_NK,
+                                                   ws.d_hascand, C.window_cap, dc);  // + has_cand, accepted = 0
+    LAUNCH_CHECK();
+    {
+        int rc = index_append(C, ws, W, C.d_blk_list.as<uint32_t>(), dc + C_ZERO, dc + C_BLK);
+        if (rc) return rc;
+        FilterArgs F = W.FA;   // the block's members against the block's (tentative) entries
+        F.epoch = C.epoch_idx; F.d_round_lo = dc + C_ZERO; F.d_round_hi = dc + C_BLK;
+        F.newbits = C.d_newbits.as<uint32_t>() + (size_t)(C.epoch_idx & 1u) * C.bm_words;
+        F.qlist = C.d_blk_list.as<uint32_t>(); F.d_nq = dc + C_BLK; F.mark = ws.d_hascand; F.count_visits = 0u;
+        F.pairs = C.d_pairsK.as<Pair>(); F.n_pairs = dc + C_NK; F.pair_cap = C.pair_cap_k;
+        F.shard_count = 1; F.shard_index = 0;   // (replicated on every process)
+        ProfScope prof(C.ctx, "filter_kernel<block>", st);
+        auto kern = C.nt ? filter_kernel<true, true> : filter_kernel<false, true>;
+        kern<<<std::min(kFilterGrid, (C.block_cap * (C.both ? 2u : 1u) + 3) / 4), 256, 0, st>>>(C.DS, F);
+    }
+    LAUNCH_CHECK();
+    // A block member without an earlier in-block candidate (has_cand clear) is certainly a
+    // new representative; only pairs against those are evaluated up front. Second round on
+    // the device: a member that has candidates but was accepted by none of the certain
+    // representatives is LIKELY a representative itself (an outlier of its family), so the
+    // pairs against those follow. Whatever the in-order walk on the host still needs
+    // afterwards goes through follow-up rounds.
+    {
+        const PairSel selK{nullptr, dc + C_NK, C.pair_cap_k, nullptr, 0, nullptr, ws.d_hascand, ws.d_accepted, b0, 0, 2048};   // (a small block: all its pairs at once, the second round then finds nothing left)
+        int rc = evaluate(C, ws, W, C.d_pairsK.as<Pair>(), selK, nullptr, 0);
+        if (rc) return rc;
+        const PairSel selK2{nullptr, dc + C_NK, C.pair_cap_k, nullptr, 0, ws.d_hascand, ws.d_accepted, nullptr, b0, 1, 0};
+        rc = evaluate(C, ws, W, C.d_pairsK.as<Pair>(), selK2, nullptr, 0);
+        if (rc) return rc;
+    }
+    // one round trip: counters, the block list, the in-block pairs (and the representatives the
+    // discovery rounds confirmed), written to host memory by one kernel
+    PubArgs pa{};
+    pa.seg[0] = {dc, C.h_cnt.p, nullptr, C_COUNT, 1, C_COUNT};
+    pa.seg[1] = {C.d_blk_list.as<uint32_t>(), C.h_blk.p, dc + C_BLK, 0, 1, C.block_cap};
+    pa.seg[2] = {C.d_pairsK.as<uint32_t>(), reinterpret_cast<uint32_t *>(C.hK.p), dc + C_NK, 0, kPairWords, C.pair_cap_k};
+    pa.n = 3;
+    if (first_block) pa.seg[pa.n++] = {C.d_new_list.as<uint32_t>(), C.h_new.p, dc + C_NEW, 0, 1, C.window_cap};
+    publish_kernel<<<64, 256, 0, st>>>(pa);
+    LAUNCH_CHECK();
+    return PGX_OK;
+}
+
+// follow-up round of the block walk: evaluate the listed pairs and fetch their records back
+int follow_up_round(ClusterCall &C, WindowSet &ws, Window &W) {
+    const hipStream_t st = ws.st;
+    const uint32_t nl = (uint32_t)C.flight.size();
+    ++C.n_rounds;
+    std::copy(C.flight.begin(), C.flight.end(), C.h_list.p);
+    PGX_HIP(hipMemcpyAsync(C.d_list.p, C.h_list.p, (size_t)nl * 4, hipMemcpyHostToDevice, st));
+    {
+        const PairSel selL{nullptr, nullptr, 0, C.d_list.as<uint32_t>(), nl, nullptr, nullptr, nullptr, W.b0, 0, 0};
+        int rc = evaluate(C, ws, W, C.d_pairsK.as<Pair>(), selL, nullptr, nl);
+        if (rc) return rc;
+    }
+    gather_pairs_kernel<<<(nl + 255) / 256, 256, 0, st>>>(C.d_pairsK.as<Pair>(), C.d_list.as<uint32_t>(), nl,
+                                                          C.d_gather.as<Pair>());
+    LAUNCH_CHECK();
+    PGX_HIP(hipMemcpyAsync(C.h_gather.p, C.d_gather.p, (size_t)nl * sizeof(Pair), hipMemcpyDeviceToHost, st));
+    PGX_HIP(spin_sync(st));
+    for (uint32_t w = 0; w < nl; ++w) C.hK.p[C.flight[w]] = C.h_gather.p[w];
+    return PGX_OK;
+}
+
+// The listed block members leave the index again (their own range of the pinned list, read by the device from
+// page-locked host memory); the block is retired, as resolved (`decided`) or given up.
+int strike_and_retire(ClusterCall &C, WindowSet &ws, Window &W, const uint32_t *list, uint32_t n_out, bool decided) {
+    W.n_struck += n_out;
+    if (n_out)
+        index_strike_kernel<<<std::min(1024u, (n_out + 3) / 4), 256, 0, ws.st>>>(C.DS, list, n_out, C.d_lines.as<IndexLine>(), W.d_poolp);
+    retire_block_kernel<<<(W.nb + 255) / 256, 256, 0, ws.st>>>(ws.d_done, ws.d_inblk, W.nb, decided ? 1u : 0u, decided ? ws.dc : nullptr);
+    LAUNCH_CHECK();
+    return PGX_OK;
+}
+
+// Blocks: members still without a representative, <= block_cap at a time, in order. A block is
+// resolved exactly: enqueue_block, the host walks the block in order (walk_block, with follow-up rounds for the pairs
+// it still needs), the entries of the members that joined a representative are struck out again, and every other
+// window member is compared with what is left: the block's new representatives. Pair work stays close to what the
+// one-by-one pass does.
+int resolve_blocks(ClusterCall &C, WindowSet &ws, Window &W) {
+    const hipStream_t st = ws.st;
+    uint32_t *const dc = ws.dc;
+    const uint32_t b0 = W.b0;
+    const uint32_t *const h_cnt = C.h_cnt.p;
+    for (bool first_block = true;;) {
+        { int rc = enqueue_block(C, ws, W, first_block); if (rc) return rc; }
+        if (first_block) {
+            // everything up to here was enqueued without looking at results: the previous window's
+            // bookkeeping runs now, behind that work, and only then is the member state reset
+            int rc = begin_host_side(C, W); if (rc) return rc;
+        }
+        PGX_HIP(spin_sync(st));
+        if (h_cnt[C_ERR]) { window_error(C, h_cnt[C_ERR], b0); return PGX_ERR_CAPACITY; }
+        if (first_block) {
+            W.n_listed = h_cnt[C_NEW];
+            for (uint32_t i = 0; i < W.n_listed; ++i) C.status[C.h_new.p[i] - b0] = ST_REP;
+            first_block = false;
+        }
+        const uint32_t n_blk = h_cnt[C_BLK], n_open = h_cnt[C_OPEN], nK = h_cnt[C_NK];
+        if (h_cnt[C_NW] > C.pair_cap) {
+            pgx_set_error("pgx_cluster_greedy: candidate pair buffer overflow (%u) in the window at %u", h_cnt[C_NW], b0);
+            return PGX_ERR_CAPACITY;
+        }
+        uint32_t *const list = C.h_push.p + W.n_struck;   // every block has its own range
+        if (nK > C.pair_cap_k) {
+            // more in-block candidate pairs than the buffer holds: give the block up (all its tentative
+            // entries are struck out again) and come back with a quarter of the members
+            if (C.block_cap <= kBlockCapMin) {
+                pgx_set_error("pgx_cluster_greedy: block pair buffer overflow (%u) in the window at %u", nK, b0);
+                return PGX_ERR_CAPACITY;
+            }
+            std::copy(C.h_blk.p, C.h_blk.p + n_blk, list);
+            int rc = strike_and_retire(C, ws, W, list, n_blk, false); if (rc) return rc;
+            C.block_cap = std::max(kBlockCapMin, C.block_cap / 4);
+            continue;
+        }
+        if (n_blk == 0) {
+            if (C.overlap) { PGX_HIP(hipEventRecord(ws.strike, st)); W.strike_recorded = true; }   // nothing tentative is left
+            break;
+        }
+        // resolve the block in order: first accepted in-block representative by (minc, index)
+        const auto t_r0 = Clock::now();
+        ++C.n_blocks;
+        C.order_k.resize(nK);
+        bucket_block_pairs(C.h_blk.p, n_blk, C.hK.p, nK, b0, C.n, C.rank_of.data(), C.bucket_k.data(), C.fill_k.data(), C.order_k.data());
+        const Block B{C.h_blk.p, n_blk, C.hK.p, nK, b0, C.n, C.bucket_k.data(), C.order_k.data()};
+        for (uint32_t t_first = 0;;) {
+            const WalkResult w = walk_block(B, t_first, C.status.data(), C.winner_key.data(), C.iden_of.data(), C.strand_of.data(), C.flight);
+            if (w == WALK_BAND) return band_error();
+            if (w == WALK_DONE) break;
+            if (C.flight.empty()) { pgx_set_error("pgx_cluster_greedy: block resolution made no progress"); return PGX_ERR_INTERNAL; }
+            int rc = follow_up_round(C, ws, W); if (rc) return rc;
+        }
+        // block decided: the candidates the one-by-one pass examines
+        if (C.count_replicated) {
+            PairCounts examined;
+            finish_block(B, C.status.data(), C.winner_key.data(), C.h_len.data(), examined);
+            add_counts(C.S, examined);
+            account(C, C.hK.p, nK);
+        }
+        C.t_resolve += seconds_since(t_r0);
+        // the members that joined a representative leave the index again; every window member is then
+        // compared with the block's representatives (the block's own members only count their visits)
+        uint32_t n_out = 0;
+        for (uint32_t t = 0; t < n_blk; ++t)
+            if (C.status[C.h_blk.p[t] - b0] != ST_REP) list[n_out++] = C.h_blk.p[t];
+        { int rc = strike_and_retire(C, ws, W, list, n_out, true); if (rc) return rc; }
+        if (C.overlap && n_open == n_blk) {   // the last block: from here on this window only reads the index
+            PGX_HIP(hipEventRecord(ws.strike, st));
+            W.strike_recorded = true;
+        }
+        { int rc = filter_new_and_evaluate(C, ws, W, dc + C_ZERO, dc + C_BLK); if (rc) return rc; }
+        if (n_open == n_blk) break;  // that was the last block
+    }
+    return PGX_OK;
+}
+
+// The discovery chunks of the windows to come. The fraction ADAPTS: a window that needed three or more blocks (the
+// discovery test certified too little: members without families) halves it for the windows after, a window with at
+// most one block raises it again.
+void adapt_chunks(ClusterCall &C, const Window &W) {
+    if (!C.chunking || W.sweep) return;
+    const uint64_t blk = C.n_blocks - W.blocks_before;
+    if (blk >= 3) C.cur_frac = std::max(0.1, C.cur_frac * 0.5);
+    else if (blk <= 1) C.cur_frac = std::min(chunk_frac_default(), C.cur_frac * 1.5);
+    C.chunk_words = std::max<uint64_t>(16384, (uint64_t)(C.cur_frac * C.thr_frac * (double)C.n_codes));
+}
+
+// ---- close the window: counters, winners, and exactly the pair records that exist, in one launch. The bookkeeping
+// becomes pending: it is deferred until the next window's first kernels are enqueued (the device starts the next
+// window right away), except where the next window's set-up needs its outcome.
+int close_window(ClusterCall &C, WindowSet &ws, Window &W) {
+    const hipStream_t st = ws.st;
+    uint32_t *const dc = ws.dc;
+    const uint32_t nb = W.nb;
+    PubArgs pa{};
+    pa.seg[0] = {dc, ws.h_ccnt.p, nullptr, C_COUNT, 1, C_COUNT};
+    pa.seg[1] = {reinterpret_cast<const uint32_t *>(ws.d_best), reinterpret_cast<uint32_t *>(ws.h_best.p), nullptr, nb, 2, nb};
+    pa.seg[2] = {reinterpret_cast<const uint32_t *>(ws.pairsW), reinterpret_cast<uint32_t *>(ws.hW.p), dc + C_NW, 0, kPairWords,
+                 (uint32_t)std::min<size_t>(ws.hW.cap, C.pair_cap)};
+    pa.n = 3;
+    if (C.both) pa.seg[pa.n++] = {reinterpret_cast<const uint32_t *>(C.d_rcvis.as<unsigned long long>()), reinterpret_cast<uint32_t *>(C.h_rcvis.p), nullptr, nb, 2, nb};
+    if (C.overlap && !W.strike_recorded) PGX_HIP(hipEventRecord(ws.strike, st));
+    publish_kernel<<<64, 256, 0, st>>>(pa);
+    LAUNCH_CHECK();
+    if (C.overlap) PGX_HIP(hipEventRecord(ws.post, st));
+    PendingWindow &pw = C.pending;
+    pw.b0 = W.b0; pw.nb = nb; pw.nW = 0; pw.sweep = W.sweep; pw.set = W.set; pw.window_words = W.window_words;
+    pw.hW = &ws.hW; pw.h_best = &ws.h_best; pw.h_ccnt = &ws.h_ccnt;
+    if (!C.overlap) { int rc = wait_closed(C, pw); if (rc) return rc; W.nW = pw.nW; }
+    const auto t_c0 = Clock::now();
+    C.pending_words = W.window_words;
+    pw.pending = true;
+    if (C.nt || C.trace2) {   // (nucleotide windows size their pair buffer from the number of representatives)
+        int rc = run_pending(C); if (rc) return rc;
+    }
+    C.t_close += seconds_since(t_c0);
+    return PGX_OK;
+}
+
+int finish_call(ClusterCall &C, uint32_t *out_n_clusters, pgx_cluster_stats *stats) {
+    pgx_cluster_stats &S = C.S;
+    if (C.trace) {
+        const double loop_s = seconds_since(C.t_loop0);
+        fprintf(stderr, "[pgx] windows %llu blocks %llu (+%llu follow-up rounds): loop %.1f ms = wait %.1f + block resolve %.1f + window close %.1f + "
+                "enqueue/other %.1f\n", (unsigned long long)S.sweeps, (unsigned long long)C.n_blocks, (unsigned long long)C.n_rounds,
+                1e3 * loop_s, 1e3 * g_wait_s, 1e3 * C.t_resolve, 1e3 * C.t_close,
+                1e3 * (seconds_since(C.t_loop0) - g_wait_s - C.t_resolve - C.t_close));
+    }
 #ifdef PGX_FTIME
     {
         unsigned long long h[16], z[16] = {0};
@@ -3678,38 +3770,122 @@ static int cluster_greedy_impl(pgx_ctx *ctx, const uint8_t *d_residues, const ui
         fprintf(stderr, "[ftime] %llu waves, %.0f clocks per wave; direct %llu, fallbacks %llu, classic %llu\n", h[12], tot / (double)h[12], h[13], h[14], h[15]);
     }
 #endif
-    if (overlap) PGX_HIP(hipStreamSynchronize(ctx->stream2));
+    if (C.overlap) PGX_HIP(hipStreamSynchronize(C.ctx->stream2));
     unsigned long long visits_table = 0;
-    PGX_HIP(hipMemcpyAsync(&visits_table, d_visits.p, 8, hipMemcpyDeviceToHost, st));
-    PGX_HIP(hipStreamSynchronize(st));
-    S.posting_visits = visits_table + visits_rc;
-    S.reserved[0] = gpu_pairs; S.reserved[1] = gpu_aligned; S.reserved[2] = gpu_aligned_bytes;
-    S.reserved[3] = filter_walk_words;
-    S.n_clusters = rep_seq.size();
+    PGX_HIP(hipMemcpyAsync(&visits_table, C.d_visits.p, 8, hipMemcpyDeviceToHost, C.st_main));
+    PGX_HIP(hipStreamSynchronize(C.st_main));
+    S.posting_visits = visits_table + C.visits_rc;
+    S.reserved[0] = C.gpu_pairs; S.reserved[1] = C.gpu_aligned; S.reserved[2] = C.gpu_aligned_bytes;
+    S.reserved[3] = C.filter_walk_words;
+    S.n_clusters = C.rep_seq.size();
 
-    phase("window loop");
+    C.phase("window loop");
     // (the outputs were written window by window, with each window's bookkeeping)
-    if (out_n_clusters) *out_n_clusters = (uint32_t)rep_seq.size();
-    if (stats) *stats = S;
+    if (out_n_clusters) *out_n_clusters = (uint32_t)C.rep_seq.size();
+    C.give_stats(stats);
     return PGX_OK;
+}
+
+}  // namespace
+
+static int cluster_greedy_impl(pgx_ctx *ctx, const uint8_t *d_residues, const uint64_t *d_offsets,
+                               uint32_t n_in, uint64_t total_in, const pgx_cluster_params *P,
+                               int32_t *out_cluster, int32_t *out_member, float *out_identity,
+                               uint8_t *out_strand, uint32_t *out_n_clusters,
+                               pgx_cluster_stats *stats, void *stream_) {
+    PGX_REQUIRE(ctx && P, "NULL argument");
+    ClusterCall C(ctx, P, (hipStream_t)stream_);
+    C.d_residues = d_residues; C.d_offsets = d_offsets; C.n_in = n_in; C.total_in = total_in;
+    C.out_cluster = out_cluster; C.out_member = out_member; C.out_identity = out_identity; C.out_strand = out_strand;
+    C.want_stats = stats != nullptr;
+    int rc;
+    if ((rc = check_params(C, out_cluster, out_member, out_identity))) return rc;
+    C.t_call0 = Clock::now();
+    C.S.n_input = n_in;
+    if (out_n_clusters) *out_n_clusters = 0;
+    C.nth = host_threads(n_in);
+    parallel_for(n_in, C.nth, [&](unsigned, size_t b, size_t e) {
+        for (size_t i = b; i < e; ++i) {
+            out_cluster[i] = -1; out_member[i] = -1; out_identity[i] = 0.f;
+            if (out_strand) out_strand[i] = 0;
+        }
+    });
+    if (n_in == 0) { C.give_stats(stats); return PGX_OK; }
+    if ((rc = order_by_length(C))) return rc;
+    if (C.n == 0) { C.give_stats(stats); return PGX_OK; }
+    if ((rc = prepare_input(C))) return rc;
+    if ((rc = build_word_lists(C))) return rc;
+    if ((rc = plan_windows(C))) return rc;
+
+    C.t_loop0 = Clock::now();
+    g_wait_s = 0.0;
+    const std::vector<uint32_t> &flush_at = C.flush_at;
+    const uint32_t n = C.n;
+    size_t next_flush = 0;
+    bool sweeping = false;
+    uint32_t sweep_at = 0;
+    for (uint32_t cursor = 0; cursor < n;) {
+        if (!sweeping && next_flush < flush_at.size() && cursor == flush_at[next_flush]) {
+            ++next_flush;
+            sweeping = true; sweep_at = cursor;
+            if ((rc = drain(C))) return rc;
+        }
+        Window W;
+        W.sweep = sweeping;
+        W.b0 = W.sweep ? sweep_at : cursor;
+        W.nb = form_window(C, W.b0, W.chunks, W.sweep || next_flush >= flush_at.size() ? n : flush_at[next_flush]);   // queries of this window
+        W.mark_absent = !flush_at.empty() && next_flush > 0;
+        W.set = C.overlap ? (int)(C.S.sweeps & 1u) : 0;   // this window's own state and stream, see WindowSet
+        WindowSet &ws = C.sets[W.set];
+        if ((rc = open_window(C, ws, W))) return rc;
+        if (W.b0 > 0 && (rc = phase_a(C, ws, W))) return rc;
+        if (W.sweep) {   // (a sweep window has neither discovery rounds nor blocks: nothing is appended)
+            if ((rc = begin_host_side(C, W))) return rc;
+        } else {
+            if ((rc = discovery_rounds(C, ws, W))) return rc;
+            if ((rc = resolve_blocks(C, ws, W))) return rc;
+        }
+        adapt_chunks(C, W);
+        if ((rc = close_window(C, ws, W))) return rc;
+        if (C.trace2)
+            fprintf(stderr, "[pgx] window %4llu b0 %8u nb %6u len %5u..%5u blocks %2llu reps +%5zu (discovery %5u) (total %7zu) pairs %7u  %.2f ms\n",
+                    (unsigned long long)C.S.sweeps, W.b0, W.nb, C.h_len[W.b0], C.h_len[W.b0 + W.nb - 1],
+                    (unsigned long long)(C.n_blocks - W.blocks_before), C.rep_seq.size() - W.n_reps, W.n_listed, C.rep_seq.size(), W.nW,
+                    1e3 * seconds_since(W.t_sweep0));
+        if (!W.sweep) { cursor += W.nb; continue; }
+        sweep_at += W.nb;
+        if (sweep_at >= n) {   // the sweep is complete: the index is emptied, clustering goes on with what is left
+            if ((rc = drain(C))) return rc;
+            PGX_HIP(hipMemsetAsync(C.d_lines.p, 0, (size_t)C.n_codes * sizeof(IndexLine), C.st_main));
+            const uint32_t one = 1u;
+            PGX_HIP(hipMemcpyAsync(C.d_idx.p, &one, 4, hipMemcpyHostToDevice, C.st_main));
+            PGX_HIP(hipStreamSynchronize(C.st_main));
+            sweeping = false;
+        }
+    }
+    if ((rc = run_pending(C))) return rc;
+    return finish_call(C, out_n_clusters, stats);
 }
 
 extern "C" int pgx_cluster_greedy(pgx_ctx *ctx, const uint8_t *residues, const uint64_t *offsets,
                                   uint32_t n_in, const pgx_cluster_params *P, int32_t *out_cluster,
                                   int32_t *out_member, float *out_identity, uint8_t *out_strand,
                                   uint32_t *out_n_clusters, pgx_cluster_stats *stats) {
-    PGX_REQUIRE(ctx && P, "NULL argument");
-    PGX_REQUIRE(n_in == 0 || (residues && offsets), "NULL sequence arrays");
-    PGX_HIP(hipSetDevice(ctx->device_id));
-    for (uint32_t i = 0; i < n_in; ++i) PGX_REQUIRE(offsets[i + 1] >= offsets[i], "offsets must be non-decreasing");
-    const uint64_t total_in = n_in ? offsets[n_in] : 0;
-    DevBuf d_res(ctx, CL_SLOT_UP_RES), d_off(ctx, CL_SLOT_UP_OFF);   // the upload buffers live in the context's workspace too
-    PGX_HIP(d_res.alloc(total_in + 16));
-    PGX_HIP(d_off.alloc(((size_t)n_in + 1) * 8));
-    if (n_in) {
-        { int rc = pgx_staged_h2d(ctx, d_res.p, residues, total_in, ctx->stream); if (rc) return rc; }   // (pageable: staged by a few threads)
-        PGX_HIP(hipMemcpyAsync(d_off.p, offsets, ((size_t)n_in + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-    }
-    return pgx_cluster_greedy_dev(ctx, d_res.as<uint8_t>(), d_off.as<uint64_t>(), n_in, total_in, P, out_cluster,
-                                  out_member, out_identity, out_strand, out_n_clusters, stats, ctx->stream);
+    const char *const fn = __func__;
+    return guarded(fn, [&]() -> int {
+        CL_REQUIRE_IN(fn, ctx && P, "NULL argument");
+        CL_REQUIRE_IN(fn, n_in == 0 || (residues && offsets), "NULL sequence arrays");
+        PGX_HIP(hipSetDevice(ctx->device_id));
+        for (uint32_t i = 0; i < n_in; ++i) CL_REQUIRE_IN(fn, offsets[i + 1] >= offsets[i], "offsets must be non-decreasing");
+        const uint64_t total_in = n_in ? offsets[n_in] : 0;
+        DevBuf d_res(ctx, CL_SLOT_UP_RES), d_off(ctx, CL_SLOT_UP_OFF);   // the upload buffers live in the context's workspace too
+        PGX_HIP(d_res.alloc(total_in + 16));
+        PGX_HIP(d_off.alloc(((size_t)n_in + 1) * 8));
+        if (n_in) {
+            { int rc = pgx_staged_h2d(ctx, d_res.p, residues, total_in, ctx->stream); if (rc) return rc; }   // (pageable: staged by a few threads)
+            PGX_HIP(hipMemcpyAsync(d_off.p, offsets, ((size_t)n_in + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+        }
+        return pgx_cluster_greedy_dev(ctx, d_res.as<uint8_t>(), d_off.as<uint64_t>(), n_in, total_in, P, out_cluster,
+                                      out_member, out_identity, out_strand, out_n_clusters, stats, ctx->stream);
+    });
 }

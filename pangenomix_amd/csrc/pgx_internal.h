@@ -149,6 +149,7 @@ template <typename T>
 struct HostVec {
     T *p = nullptr;
     size_t n = 0;
+    HostVec() = default;   // bound later, by assignment
     HostVec(pgx_ctx *ctx, HostSlot slot, size_t count) { bind(ctx, slot, count); }
     HostVec(pgx_ctx *ctx, HostSlot slot, size_t count, T fill) {
         bind(ctx, slot, count);
