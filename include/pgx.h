@@ -1060,6 +1060,45 @@ int pgx_tree_content_dev(pgx_ctx *ctx, const uint64_t *d_bits, uint32_t n_genes,
                          uint64_t n_edges, const uint32_t *d_order, const uint32_t *level_off, uint32_t n_levels,
                          uint32_t *d_out_counts, uint32_t *d_out_totals, void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* Exact search for variable-length patterns in a text, with positions and counts (the primitive under pangenomix_amd.mlst; the
+ * reference's pangenome_analysis.py:402-453 run_mlst shells out to an external program). Pattern k is the bytes
+ * [pattern_offsets[k], pattern_offsets[k + 1]) of a blob (the conventions of pgx_dict_load: n + 1 offsets that never decrease,
+ * the blob is the bytes [0, offsets[n])), L_k of them; text is text_bytes raw bytes;
+ *   first[k] = the smallest i with text[i .. i + L_k) == pattern k, 0xFFFFFFFF for none
+ *   count[k] = the number of such i; overlapping occurrences are each counted
+ * Bytes are compared as bytes (no case folding, no alphabet, values >= 0x80 allowed); equal patterns given twice both get the
+ * full answer. A pattern never matches past text_bytes and nothing at or beyond text_bytes is read. Both outputs are a minimum /
+ * an integer sum over a set (atomicMin, atomicAdd, one lane per verified occurrence): the same input gives the same bytes on
+ * every call. Only the first `seed` (1..64) bytes of a pattern are hashed, and hashes only decide where to look -- an
+ * occurrence is counted after all L_k bytes have been compared -- so the result is exact; PGX_PATTERN_NARROW_HASH (a test
+ * seam) keeps only the low 3 bits of every hash: same results, every position is verified against every pattern.
+ * seed outside 1..64, text_bytes >= 2^32, n_patterns >= 2^24, unknown flags, too small or misaligned a workspace, and in the
+ * host entries a blob of 2^32 bytes or more, decreasing offsets or a pattern shorter than seed fail with PGX_ERR_INVALID before
+ * anything is launched or written. n_patterns = 0 does nothing; a text shorter than seed (text_bytes = 0 included) gives
+ * first = 0xFFFFFFFF and count = 0 everywhere.
+ *   pgx_pattern_load      HOST pointers: keeps the patterns, their offsets and their table in the context, replacing an
+ *                         earlier set (a refused load leaves the earlier set loaded)
+ *   pgx_pattern_query     HOST pointers: searches `text` for the set loaded last (PGX_ERR_INVALID without one), with the seed
+ *                         and flags it was loaded with; any number of calls per load. out_first, out_count: [n_patterns]
+ *   pgx_pattern_scan_dev  text, patterns, offsets (8-byte aligned), first and count (4-byte aligned) and the workspace
+ *                         (pgx_pattern_workspace_bytes(), 16-byte aligned; 0 for sizes that are refused) are the caller's
+ *                         DEVICE pointers; the text may start at any address. Plain launches on `stream`, which is
+ *                         synchronised once at the end; inputs are not written, nothing outside first, count and the
+ *                         workspace is. Device offsets are not checked, and the LAST offset is taken as the blob's size: the
+ *                         kernels clamp every pattern into [0, last offset), so with a last offset inside the caller's
+ *                         allocation nothing outside it is read whatever the other offsets hold. A pattern that is shorter
+ *                         than seed after clamping matches nowhere; the result for broken offsets is otherwise unspecified.
+ * pgx_pattern_scan_tile(): the text positions one workgroup takes at a time. */
+#define PGX_PATTERN_NARROW_HASH 1u   /* keep only the low 3 bits of every hash: same results, every probe collides */
+uint32_t pgx_pattern_scan_tile(void);
+size_t pgx_pattern_workspace_bytes(uint64_t pattern_bytes, uint32_t n_patterns);
+int pgx_pattern_load(pgx_ctx *ctx, const uint8_t *patterns, const uint64_t *pattern_offsets, uint32_t n_patterns, uint32_t seed,
+                     uint32_t flags);
+int pgx_pattern_query(pgx_ctx *ctx, const uint8_t *text, uint64_t text_bytes, uint32_t *out_first, uint32_t *out_count);
+int pgx_pattern_scan_dev(pgx_ctx *ctx, const uint8_t *d_text, uint64_t text_bytes, const uint8_t *d_patterns,
+                         const uint64_t *d_pattern_offsets, uint32_t n_patterns, uint32_t seed, uint32_t flags,
+                         uint32_t *d_first, uint32_t *d_count, void *d_workspace, size_t workspace_bytes, void *stream);
+
 /* feature names (pangenome.py:1944-1969) as fixed-width zero-padded ASCII records (numpy 'S<width>'):
  * <prefix><cluster>[<variant><member>]; variant NULL = gene names */
 int pgx_format_labels(const char *prefix, const char *variant, const int32_t *cluster, const int32_t *member,

@@ -71,7 +71,8 @@ FCD_OVERLAP, FCD_DIM_BALANCE = 1, 2    # PGX_FCD_OVERLAP, PGX_FCD_DIM_BALANCE
 BERNOULLI_CD_LOGS = 1                  # PGX_BERNOULLI_CD_LOGS
 ASSOC_BLOCKS, ASSOC_DROP_EMPTY = 1, 2  # PGX_ASSOC_BLOCKS, PGX_ASSOC_DROP_EMPTY
 DICT_NARROW_HASH = 1                   # PGX_DICT_NARROW_HASH
-PROX_NARROW_HASH = 1                   # PGX_PROX_NARROW_HASH
+PATTERN_NARROW_HASH = 1                # PGX_PATTERN_NARROW_HASH
+PROX_NARROW_HASH = 1                 # PGX_PROX_NARROW_HASH
 ANNOT_NARROW_HASH = 1                  # PGX_ANNOT_NARROW_HASH
 ASSOC_NARROW_HASH = 4                  # PGX_ASSOC_NARROW_HASH
 TERM_FOLD_ASCII = 1                    # PGX_TERM_FOLD_ASCII
@@ -233,6 +234,12 @@ SIGNATURES = {
                                    _P, C.POINTER(C.c_uint64)]),
     'pgx_tree_content_dev': (C.c_int, [_P, _P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_uint32, C.c_uint64, _P, _P, C.c_uint32, _P,
                                        _P, _P, C.c_size_t, _P]),
+    'pgx_pattern_scan_tile': (C.c_uint32, []),
+    'pgx_pattern_workspace_bytes': (C.c_size_t, [C.c_uint64, C.c_uint32]),
+    'pgx_pattern_load': (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32]),
+    'pgx_pattern_query': (C.c_int, [_P, _P, C.c_uint64, _P, _P]),
+    'pgx_pattern_scan_dev': (C.c_int, [_P, _P, C.c_uint64, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_size_t,
+                                       _P]),
     'pgx_genome_sets_diff':(C.c_int, [_P, _P, _P, C.c_uint64, _P, _P, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P]),
     'pgx_genome_sets_diff_dev': (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P]),
     'pgx_cluster_greedy': (C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(ClusterParams), _P, _P, _P, _P,
@@ -1025,6 +1032,36 @@ class Context(object):
         """Both on device memory (raw device addresses, None for no first; synchronises `stream`, see pgx.h)."""
         check(lib().pgx_dict_match_dev(self._h, d_keys, d_key_offsets, int(n_keys), d_queries, d_query_offsets, int(n_queries),
                                        int(flags), d_out_first, d_out_last, d_ws, int(ws_bytes), stream))
+
+    # -- variable-length patterns in a text, with positions and counts (pangenomix_amd.mlst) --------------------------------
+    def pattern_load(self, patterns, pattern_offsets, seed, flags=0):
+        """Loads the patterns -- pattern k is the bytes patterns[pattern_offsets[k]:pattern_offsets[k + 1]] -- for
+        pattern_query, replacing an earlier set. seed: the leading bytes that are hashed, 1..64 and no longer than the shortest
+        pattern (pgx.h: pgx_pattern_load). flags: PATTERN_NARROW_HASH, the test seam. Returns the number of patterns."""
+        patterns, pattern_offsets = self._string_args(patterns, pattern_offsets)
+        check(lib().pgx_pattern_load(self._h, _ptr(patterns), _ptr(pattern_offsets), pattern_offsets.size - 1, int(seed),
+                                     int(flags)))
+        self._pattern_count = pattern_offsets.size - 1
+        return self._pattern_count
+
+    def pattern_query(self, text):
+        """(first, count) uint32 [n_patterns] of the loaded patterns in `text` (bytes or a 1-D uint8 array): the smallest
+        position of an occurrence, 0xFFFFFFFF for none, and the number of occurrences (pgx.h: pgx_pattern_query)."""
+        if isinstance(text, (bytes, bytearray, memoryview)):
+            text = np.frombuffer(text, dtype=np.uint8)
+        text = np.ascontiguousarray(text, dtype=np.uint8)
+        if text.ndim != 1:
+            raise ValueError('text must be 1-D')
+        n = getattr(self, '_pattern_count', 0)
+        first, count = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32)
+        check(lib().pgx_pattern_query(self._h, _ptr(text), text.size, _ptr(first), _ptr(count)))
+        return first, count
+
+    def pattern_scan_dev(self, d_text, text_bytes, d_patterns, d_pattern_offsets, n_patterns, seed, d_first, d_count, d_ws,
+                         ws_bytes, flags=0, stream=0):
+        """Load and query in one on device memory (raw device addresses; synchronises `stream`, see pgx.h)."""
+        check(lib().pgx_pattern_scan_dev(self._h, d_text, int(text_bytes), d_patterns, d_pattern_offsets, int(n_patterns),
+                                         int(seed), int(flags), d_first, d_count, d_ws, int(ws_bytes), stream))
 
     def genome_sets_diff(self, a_rows, a_genomes, b_rows, b_genomes, n_rows, n_genomes):
         """(a_only, b_only) uint32 [n_genomes]: per genome the rows of the COO set A that B lacks and the other way round;

@@ -81,6 +81,9 @@ enum DevSlot : int {        // pgx_ctx::arena, through DevBuf
     TG_SLOT_IN, TG_SLOT_WS, TG_SLOT_OUT, MI_SLOT_TABLES, MI_SLOT_ROWS, MI_SLOT_OUT,
     // tree.hip: the species' table, the tree arrays in one, counts and totals in one
     TR_SLOT_BITS, TR_SLOT_ROWS, TR_SLOT_SPECIES, TR_SLOT_CNT, TR_SLOT_IN, TR_SLOT_OUT,
+    // pattern.hip: the loaded set stays in the first three (blob, offsets, table and filter); then a query's text and its
+    // first and count in one
+    PT_SLOT_PATTERNS, PT_SLOT_OFFSETS, PT_SLOT_WS, PT_SLOT_TEXT, PT_SLOT_OUT,
     DEV_SLOT_COUNT
 };
 enum HostSlot : int {       // pgx_ctx::host_scratch, through HostVec
@@ -134,6 +137,11 @@ struct pgx_ctx {
     bool dict_loaded = false;
     uint32_t dict_keys = 0, dict_flags = 0;
     const void *dict_d_keys = nullptr, *dict_d_offsets = nullptr, *dict_d_table = nullptr;
+    // the set of patterns loaded for exact scans (pgx_pattern_load): how many, the seed and flags they were hashed with, and
+    // the device pointers of blob, offsets and table + filter (workspace slots only pattern.hip uses; valid while pattern_loaded)
+    bool pattern_loaded = false;
+    uint32_t pattern_count = 0, pattern_seed = 0, pattern_flags = 0;
+    const void *pattern_d_blob = nullptr, *pattern_d_offsets = nullptr, *pattern_d_ws = nullptr;
     // the concepts of the last formal concept decomposition (pgx_fcd*), kept for pgx_fcd_fetch: row / column indices of
     // all concepts end to end, the offsets of each concept in them (n + 1 entries), the ones left uncovered after each
     std::vector<int32_t> fcd_rows, fcd_cols;

@@ -387,3 +387,68 @@ def phylogeny(n_species, seed, n_genes=100, max_children=4, mapped_internal=0, u
     index = np.array(['G%d' % g for g in range(n_genes)], dtype=object)
     columns = np.array(['S%d' % s for s in range(n_species)] + ['X%d' % s for s in range(unused_species)], dtype=object)
     return G, root, mrca_to_species, sparse_utils.LightSparseDataFrame(index, columns, data)
+
+
+def mlst_scheme(n_loci=7, n_alleles=300, length=450, seed=21, max_mutations=3):
+    """A synthetic typing scheme (pangenomix_amd.mlst.Scheme): n_loci loci of n_alleles distinct alleles of `length` bases,
+    numbered from 1. The alleles of a locus are point mutants of one ancestor (1..max_mutations substitutions anywhere), so
+    most of them share their first 32 bases and long stretches behind them. 50 profiles of random alleles, ST 1..50."""
+    from . import mlst
+    rng = np.random.default_rng(seed)
+    letters = np.frombuffer(b'ACGT', dtype=np.uint8)
+    loci = ['loc%c' % (ord('A') + i) if n_loci <= 26 else 'loc%d' % i for i in range(n_loci)]
+    alleles = {}
+    for locus in loci:
+        ancestor = letters[rng.integers(0, 4, length)]
+        seen, records = set(), []
+        while len(records) < n_alleles:
+            a = ancestor.copy()
+            for at in rng.integers(0, length, int(rng.integers(1, max_mutations + 1))).tolist():
+                a[at] = letters[(int(np.flatnonzero(letters == a[at])[0]) + int(rng.integers(1, 4))) % 4]
+            raw = a.tobytes()
+            if raw not in seen:
+                seen.add(raw)
+                records.append((len(records) + 1, raw))
+        alleles[locus] = records
+    profiles = {}
+    for st in range(1, 51):
+        profiles.setdefault(tuple(int(x) for x in rng.integers(1, n_alleles + 1, n_loci)), str(st))
+    return mlst.Scheme('synth', loci, alleles, profiles)
+
+
+def write_mlst_scheme(scheme, scheme_dir):
+    """The scheme as the files pangenomix_amd.mlst.load_scheme reads"""
+    os.makedirs(scheme_dir, exist_ok=True)
+    for locus in scheme.loci:
+        with open(os.path.join(scheme_dir, locus + '.tfa'), 'wb') as f:
+            for number, seq in scheme.alleles[locus]:
+                f.write(b'>%s_%d\n%s\n' % (locus.encode('ascii'), number, seq))
+    with open(os.path.join(scheme_dir, scheme.name + '.txt'), 'w') as f:
+        f.write('\t'.join(['ST'] + list(scheme.loci) + ['clonal_complex']) + '\n')
+        for key, st in scheme.profiles.items():
+            f.write('\t'.join([st] + [str(n) for n in key] + ['']) + '\n')
+
+
+def mlst_genome(scheme, path, carried, n_bp=200000, n_contigs=5, seed=0, novel=()):
+    """Writes an FNA of n_contigs random contigs, n_bp bases in all, that carries the alleles `carried`: {locus: (number,
+    strand)} with strand '+' or '-' (a locus that is no key is absent). A locus in `novel` carries its allele with one base
+    changed to a sequence the scheme does not hold. No allele lies across a contig joint. Returns the path."""
+    rng = np.random.default_rng(seed)
+    letters = np.frombuffer(b'ACGT', dtype=np.uint8)
+    contigs = [bytearray(letters[rng.integers(0, 4, n_bp // n_contigs)].tobytes()) for _ in range(n_contigs)]
+    for i, (locus, (number, strand)) in enumerate(sorted(carried.items())):
+        known = {seq for _, seq in scheme.alleles[locus]}
+        seq = dict(scheme.alleles[locus])[number]
+        at = len(seq) // 2
+        while locus in novel and seq in known:
+            seq = seq[:at] + b'ACGT'[(b'ACGT'.index(seq[at:at + 1]) + 1) % 4:][:1] + seq[at + 1:]
+            at += 1
+        contig = contigs[i % n_contigs]
+        place = (i // n_contigs + 1) * (len(seq) + 100)
+        contig[place:place + len(seq)] = seq if strand == '+' else _revcomp(seq)
+    with open(path, 'wb') as f:
+        for c, contig in enumerate(contigs):
+            f.write(b'>contig%d\n' % (c + 1))
+            for j in range(0, len(contig), 80):
+                f.write(bytes(contig[j:j + 80]) + b'\n')
+    return path

@@ -1,0 +1,145 @@
+#!/usr/bin/env python
+"""Timing of MLST typing and of the pattern scan under it. Prints one JSON object.
+
+    python tools/mlst_bench.py [--runs 5] [--genomes 16] [--out profiles/mlst_bench.json]
+
+The input is synthetic (pangenomix_amd.synth): a genome of --bases (5 Mbp) of random ACGT in --contigs (50) contigs that carries
+one allele of every locus, half of them on the minus strand, and two schemes of 7 loci x 450 bases, one of 300 and one of
+3,000 alleles per locus (point mutants of one ancestor per locus, so most alleles of a locus share their seed). Per scheme,
+median / min / max of --runs runs after a warm-up, in one process on one machine:
+  pattern_load, pattern_query   the two library calls with their transfers
+  kernel_ms                     per-kernel time of ONE profiled load + query (pgx_profile_read; a run of its own)
+  yardstick                     scan_kernel (csrc/scan.hip, the code of the parent commit, unchanged here) on the same text with
+                                window = seed and as many keys as the patterns have distinct seeds: the same per-position work
+                                without any verification; ratio = pattern_scan_kernel / scan_kernel
+  call_alleles                  per genome over --genomes copies of the genome file (links to one file; each is read and parsed
+                                again), with ctx and with ctx=None
+"""
+import argparse
+import contextlib
+import json
+import os
+import sys
+import tempfile
+import threading
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from pangenomix_amd import _native, mlst, synth           # noqa: E402
+
+
+def timed(fn, runs):
+    fn()
+    t = []
+    for _ in range(runs):
+        t0 = time.perf_counter()
+        out = fn()
+        t.append(time.perf_counter() - t0)
+    return {'median': float(np.median(t)), 'min': min(t), 'max': max(t)}, out
+
+
+def note(*words):
+    print(*words, file=sys.stderr, flush=True)
+
+
+@contextlib.contextmanager
+def heartbeat(what, every=60.0):
+    """a line on stderr every `every` seconds while the block runs"""
+    done = threading.Event()
+
+    def run():
+        t0 = time.perf_counter()
+        while not done.wait(every):
+            note('... %s: %.0f s so far' % (what, time.perf_counter() - t0))
+    thread = threading.Thread(target=run, daemon=True)
+    thread.start()
+    try:
+        yield
+    finally:
+        done.set()
+        thread.join()
+
+
+def profiled(ctx, fn):
+    ctx.profile(True)
+    ctx.profile_reset()
+    fn()
+    kern = {k: {'ms': ms, 'launches': n} for k, (ms, n) in ctx.profile_read().items()}
+    ctx.profile(False)
+    return kern
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--runs', type=int, default=5)
+    ap.add_argument('--genomes', type=int, default=16)
+    ap.add_argument('--bases', type=int, default=5000000)
+    ap.add_argument('--contigs', type=int, default=50)
+    ap.add_argument('--alleles', type=int, nargs='+', default=[300, 3000])
+    ap.add_argument('--out', default=None)
+    args = ap.parse_args()
+    ctx = _native.Context(0)
+    out = {'device': ctx.device_info()['name'], 'runs': args.runs, 'genomes': args.genomes, 'bases': args.bases,
+           'contigs': args.contigs, 'schemes': {}}
+    with tempfile.TemporaryDirectory() as tmp:
+        for n_alleles in args.alleles:
+            scheme = synth.mlst_scheme(n_loci=7, n_alleles=n_alleles, length=450, seed=21)
+            key, st = next(iter(scheme.profiles.items()))
+            carried = {locus: (number, '+-'[i % 2]) for i, (locus, number) in enumerate(zip(scheme.loci, key))}
+            first = synth.mlst_genome(scheme, os.path.join(tmp, 'g%d_0.fna' % n_alleles), carried, n_bp=args.bases,
+                                      n_contigs=args.contigs, seed=3)
+            paths = [first]
+            for g in range(1, args.genomes):
+                paths.append(os.path.join(tmp, 'g%d_%d.fna' % (n_alleles, g)))
+                os.symlink(first, paths[-1])
+            note('scheme 7 x %d x 450: files written' % n_alleles)
+            pats = mlst._Patterns(scheme)
+            text = b'\x00'.join(mlst.read_genome(first)[1])
+            seeds = sorted({p[:pats.seed] for p in pats.patterns})
+            rec = {'patterns': len(pats.patterns), 'pattern_bytes': int(pats.blob.size), 'seed': pats.seed,
+                   'distinct_seeds': len(seeds), 'text_bytes': len(text)}
+            rec['pattern_load'], _ = timed(lambda: ctx.pattern_load(pats.blob, pats.offsets, seed=pats.seed), args.runs)
+            rec['pattern_query'], (hit_first, hit_count) = timed(lambda: ctx.pattern_query(text), args.runs)
+            want = mlst.host_scan(text, pats.patterns, pats.seed)
+            assert np.array_equal(hit_first, want[0]) and np.array_equal(hit_count, want[1]) and int(hit_count.sum()) == 7
+            kern = profiled(ctx, lambda: (ctx.pattern_load(pats.blob, pats.offsets, seed=pats.seed), ctx.pattern_query(text)))
+            rec['kernel_ms'] = kern
+            keys = np.frombuffer(b''.join(seeds), dtype=np.uint8).reshape(len(seeds), pats.seed)
+            rec['window_scan'], found = timed(lambda: ctx.window_scan(text, keys), args.runs)
+            base = profiled(ctx, lambda: ctx.window_scan(text, keys))
+            a, b = kern.get('pattern_scan_kernel', {}).get('ms', 0), base.get('scan_kernel', {}).get('ms', 0)
+            rec['yardstick'] = {'what': 'scan_kernel of csrc/scan.hip on the same text, window = seed, keys = the distinct seeds',
+                                'keys': len(seeds), 'keys_found': int(found.sum()), 'kernel_ms': base,
+                                'pattern_scan_kernel_ms': a, 'scan_kernel_ms': b, 'ratio': a / b if b > 0 else None}
+            note('library calls and kernels timed, ratio', rec['yardstick']['ratio'])
+            mlst.MLST_PATH_COUNTS.clear()
+            mlst.call_alleles(scheme, paths[:2], ctx=ctx)                                            # warm-up
+            t0 = time.perf_counter()
+            frame = mlst.call_alleles(scheme, paths, ctx=ctx)
+            dev_s = time.perf_counter() - t0
+            note('call_alleles with ctx: %.3f s for %d genomes' % (dev_s, args.genomes))
+            with heartbeat('call_alleles with ctx=None'):                        # minutes of host work at 3,000 alleles
+                t0 = time.perf_counter()
+                host_frame = mlst.call_alleles(scheme, paths)
+                host_s = time.perf_counter() - t0
+            note('call_alleles with ctx=None: %.3f s' % host_s)
+            assert frame.equals(host_frame) and (frame['ST'] == st).all()
+            assert mlst.MLST_PATH_COUNTS == {'device': args.genomes + 2, 'host': args.genomes}
+            rec['read_genome'], _ = timed(lambda: mlst.read_genome(first), args.runs)
+            rec['call_alleles'] = {'ctx_seconds_per_genome': dev_s / args.genomes, 'host_seconds_per_genome': host_s / args.genomes,
+                                   'host_over_ctx': host_s / dev_s}
+            out['schemes']['7x%dx450' % n_alleles] = rec
+    ctx.close()
+    text = json.dumps(out, indent=1, sort_keys=True)
+    if args.out:
+        with open(args.out, 'w') as f:
+            f.write(text + '\n')
+    print(json.dumps(out))
+
+
+if __name__ == '__main__':
+    main()
