@@ -1099,6 +1099,53 @@ int pgx_pattern_scan_dev(pgx_ctx *ctx, const uint8_t *d_text, uint64_t text_byte
                          const uint64_t *d_pattern_offsets, uint32_t n_patterns, uint32_t seed, uint32_t flags,
                          uint32_t *d_first, uint32_t *d_count, void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* Bounded-mismatch search for variable-length patterns in a text (the primitive under the novel-allele calls of
+ * pangenomix_amd.mlst). Pattern k is the bytes [pattern_offsets[k], pattern_offsets[k + 1]) of a blob (the conventions of
+ * pgx_pattern_load), L_k of them; max_mismatch[k] (uint8) is m_k; text is text_bytes raw bytes; separator is a byte value
+ * 0..255 or PGX_NEAR_NO_SEPARATOR; active is one uint8 per pattern, or NULL for all patterns. A WINDOW of pattern k is a
+ * position i with i + L_k <= text_bytes whose L_k text bytes do not hold `separator`, and
+ *   d_k(i)  = #{ j : text[i + j] != pattern_k[j] }
+ *   best[k] = min over windows i with d_k(i) <= m_k of (d_k(i) << 32 | i)
+ *           = 0xFFFFFFFFFFFFFFFF when there is none, or when active[k] == 0
+ * Bytes are compared as bytes (no case folding, no alphabet, values >= 0x80 allowed). A window never reaches past text_bytes
+ * and nothing at or beyond text_bytes is read. best is a minimum over a set (a 64-bit atomicMin), so the same input gives the
+ * same bytes on every call. Exact occurrences are included: d = 0, and the low word is then pgx_pattern_query's first. There
+ * is NO occurrence count: a window is reached once for every indexed block that survived in it, and a sum would count it
+ * that often.
+ * The index: pattern k contributes its first m_k + 1 non-overlapping blocks of `block` (1..64) bytes, at offsets 0, block,
+ * 2 * block, ... At most m_k mismatches cannot touch all m_k + 1 disjoint blocks, so every qualifying window holds at least
+ * one of them exactly at its place and is found. Hashes only decide where to look -- a distance is counted over all L_k
+ * bytes -- so the result is exact; PGX_NEAR_NARROW_HASH (a test seam) keeps only the low 3 bits of every hash: same results.
+ * block outside 1..64, text_bytes >= 2^32, n_patterns >= 2^24, separator > 0x100, unknown flags, 2^30 blocks or more, too small
+ * or misaligned a workspace, and in the host entries a blob of 2^32 bytes or more, decreasing offsets or a pattern with
+ * (m_k + 1) * block > L_k fail with PGX_ERR_INVALID before anything is launched or written. n_patterns = 0 does nothing; a
+ * text shorter than block (text_bytes = 0 included) gives all-ones everywhere.
+ *   pgx_near_load      HOST pointers: keeps the patterns, their offsets, max_mismatch and the table in the context, replacing
+ *                      an earlier set (a refused load leaves the earlier set loaded)
+ *   pgx_near_query     HOST pointers: searches `text` for the set loaded last (PGX_ERR_INVALID without one), with the block
+ *                      and flags it was loaded with; any number of calls per load. out_best: [n_patterns]
+ *   pgx_near_scan_dev  text, patterns, offsets and best (8-byte aligned), max_mismatch, active (or NULL) and the workspace
+ *                      (pgx_near_workspace_bytes(), 16-byte aligned; 0 for sizes that are refused) are the caller's DEVICE
+ *                      pointers; the text may start at any address. n_blocks is the number of table entries the workspace was
+ *                      sized for: the caller's sum of m_k + 1; blocks beyond it are not inserted. Plain launches on `stream`,
+ *                      which is synchronised once at the end; no allocation; inputs are not written, nothing outside best and
+ *                      the workspace is. Device offsets are not checked, and the LAST offset is taken as the blob's size: the
+ *                      kernels clamp every pattern into [0, last offset) as pgx_pattern_scan_dev's do. A block that does not
+ *                      fit its clamped pattern is not inserted; the result for such patterns is otherwise unspecified.
+ * pgx_near_scan_tile(): the text positions one workgroup takes at a time. */
+#define PGX_NEAR_NARROW_HASH 1u      /* keep only the low 3 bits of every hash: same results, every probe collides */
+#define PGX_NEAR_NO_SEPARATOR 0x100u /* no byte value ends a window */
+uint32_t pgx_near_scan_tile(void);
+size_t pgx_near_workspace_bytes(uint64_t pattern_bytes, uint32_t n_patterns, uint64_t n_blocks);
+int pgx_near_load(pgx_ctx *ctx, const uint8_t *patterns, const uint64_t *pattern_offsets, uint32_t n_patterns,
+                  const uint8_t *max_mismatch, uint32_t block, uint32_t flags);
+int pgx_near_query(pgx_ctx *ctx, const uint8_t *text, uint64_t text_bytes, uint32_t separator, const uint8_t *active,
+                   uint64_t *out_best);
+int pgx_near_scan_dev(pgx_ctx *ctx, const uint8_t *d_text, uint64_t text_bytes, uint32_t separator, const uint8_t *d_patterns,
+                      const uint64_t *d_pattern_offsets, uint32_t n_patterns, const uint8_t *d_max_mismatch, uint32_t block,
+                      uint64_t n_blocks, uint32_t flags, const uint8_t *d_active, uint64_t *d_best, void *d_workspace,
+                      size_t workspace_bytes, void *stream);
+
 /* feature names (pangenome.py:1944-1969) as fixed-width zero-padded ASCII records (numpy 'S<width>'):
  * <prefix><cluster>[<variant><member>]; variant NULL = gene names */
 int pgx_format_labels(const char *prefix, const char *variant, const int32_t *cluster, const int32_t *member,

@@ -72,6 +72,8 @@ BERNOULLI_CD_LOGS = 1                  # PGX_BERNOULLI_CD_LOGS
 ASSOC_BLOCKS, ASSOC_DROP_EMPTY = 1, 2  # PGX_ASSOC_BLOCKS, PGX_ASSOC_DROP_EMPTY
 DICT_NARROW_HASH = 1                   # PGX_DICT_NARROW_HASH
 PATTERN_NARROW_HASH = 1                # PGX_PATTERN_NARROW_HASH
+NEAR_NARROW_HASH = 1                   # PGX_NEAR_NARROW_HASH
+NEAR_NO_SEPARATOR = 0x100              # PGX_NEAR_NO_SEPARATOR
 PROX_NARROW_HASH = 1                 # PGX_PROX_NARROW_HASH
 ANNOT_NARROW_HASH = 1                  # PGX_ANNOT_NARROW_HASH
 ASSOC_NARROW_HASH = 4                  # PGX_ASSOC_NARROW_HASH
@@ -240,6 +242,12 @@ SIGNATURES = {
     'pgx_pattern_query': (C.c_int, [_P, _P, C.c_uint64, _P, _P]),
     'pgx_pattern_scan_dev': (C.c_int, [_P, _P, C.c_uint64, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_size_t,
                                        _P]),
+    'pgx_near_scan_tile': (C.c_uint32, []),
+    'pgx_near_workspace_bytes': (C.c_size_t, [C.c_uint64, C.c_uint32, C.c_uint64]),
+    'pgx_near_load': (C.c_int, [_P, _P, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32]),
+    'pgx_near_query': (C.c_int, [_P, _P, C.c_uint64, C.c_uint32, _P, _P]),
+    'pgx_near_scan_dev': (C.c_int, [_P, _P, C.c_uint64, C.c_uint32, _P, _P, C.c_uint32, _P, C.c_uint32, C.c_uint64, C.c_uint32,
+                                    _P, _P, _P, C.c_size_t, _P]),
     'pgx_genome_sets_diff':(C.c_int, [_P, _P, _P, C.c_uint64, _P, _P, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P]),
     'pgx_genome_sets_diff_dev': (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P]),
     'pgx_cluster_greedy': (C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(ClusterParams), _P, _P, _P, _P,
@@ -1062,6 +1070,47 @@ class Context(object):
         """Load and query in one on device memory (raw device addresses; synchronises `stream`, see pgx.h)."""
         check(lib().pgx_pattern_scan_dev(self._h, d_text, int(text_bytes), d_patterns, d_pattern_offsets, int(n_patterns),
                                          int(seed), int(flags), d_first, d_count, d_ws, int(ws_bytes), stream))
+
+    # -- variable-length patterns in a text within a number of mismatches (pangenomix_amd.mlst, novel alleles) ----------------
+    def near_load(self, patterns, pattern_offsets, max_mismatch, block, flags=0):
+        """Loads the patterns for near_query, replacing an earlier set. max_mismatch: uint8 [n_patterns]; block: the bytes of
+        an indexed block, 1..64, with (max_mismatch[k] + 1) * block <= the length of pattern k (pgx.h: pgx_near_load). flags:
+        NEAR_NARROW_HASH, the test seam. Returns the number of patterns."""
+        patterns, pattern_offsets = self._string_args(patterns, pattern_offsets)
+        n = pattern_offsets.size - 1
+        if np.size(max_mismatch) and (np.min(max_mismatch) < 0 or np.max(max_mismatch) > 255):
+            raise ValueError('max_mismatch must be 0..255')
+        max_mismatch = np.ascontiguousarray(max_mismatch, dtype=np.uint8)
+        if max_mismatch.shape != (n,):
+            raise ValueError('max_mismatch must hold one entry per pattern')
+        check(lib().pgx_near_load(self._h, _ptr(patterns), _ptr(pattern_offsets), n, _ptr(max_mismatch), int(block), int(flags)))
+        self._near_count = n
+        return n
+
+    def near_query(self, text, separator=NEAR_NO_SEPARATOR, active=None):
+        """best uint64 [n_patterns] of the loaded patterns in `text` (bytes or a 1-D uint8 array): mismatches << 32 | position
+        of the best window within max_mismatch, all-ones for none and for a pattern whose `active` (uint8 [n_patterns], None:
+        all) is 0 (pgx.h: pgx_near_query)."""
+        if isinstance(text, (bytes, bytearray, memoryview)):
+            text = np.frombuffer(text, dtype=np.uint8)
+        text = np.ascontiguousarray(text, dtype=np.uint8)
+        if text.ndim != 1:
+            raise ValueError('text must be 1-D')
+        n = getattr(self, '_near_count', 0)
+        if active is not None:
+            active = np.ascontiguousarray(active, dtype=np.uint8)
+            if active.shape != (n,):
+                raise ValueError('active must hold one entry per pattern')
+        best = np.zeros(n, dtype=np.uint64)
+        check(lib().pgx_near_query(self._h, _ptr(text), text.size, int(separator), _ptr(active), _ptr(best)))
+        return best
+
+    def near_scan_dev(self, d_text, text_bytes, separator, d_patterns, d_pattern_offsets, n_patterns, d_max_mismatch, block,
+                      n_blocks, d_active, d_best, d_ws, ws_bytes, flags=0, stream=0):
+        """Load and query in one on device memory (raw device addresses, None for no active; synchronises `stream`, see pgx.h)."""
+        check(lib().pgx_near_scan_dev(self._h, d_text, int(text_bytes), int(separator), d_patterns, d_pattern_offsets,
+                                      int(n_patterns), d_max_mismatch, int(block), int(n_blocks), int(flags), d_active, d_best,
+                                      d_ws, int(ws_bytes), stream))
 
     def genome_sets_diff(self, a_rows, a_genomes, b_rows, b_genomes, n_rows, n_genomes):
         """(a_only, b_only) uint32 [n_genomes]: per genome the rows of the COO set A that B lacks and the other way round;

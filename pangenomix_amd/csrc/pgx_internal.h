@@ -84,6 +84,9 @@ enum DevSlot : int {        // pgx_ctx::arena, through DevBuf
     // pattern.hip: the loaded set stays in the first three (blob, offsets, table and filter); then a query's text and its
     // first and count in one
     PT_SLOT_PATTERNS, PT_SLOT_OFFSETS, PT_SLOT_WS, PT_SLOT_TEXT, PT_SLOT_OUT,
+    // near.hip: the loaded set stays in the first four (blob, offsets, max_mismatch, table and filter); then a query's text,
+    // its active flags and its best
+    NR_SLOT_PATTERNS, NR_SLOT_OFFSETS, NR_SLOT_MISMATCH, NR_SLOT_WS, NR_SLOT_TEXT, NR_SLOT_ACTIVE, NR_SLOT_OUT,
     DEV_SLOT_COUNT
 };
 enum HostSlot : int {       // pgx_ctx::host_scratch, through HostVec
@@ -142,6 +145,13 @@ struct pgx_ctx {
     bool pattern_loaded = false;
     uint32_t pattern_count = 0, pattern_seed = 0, pattern_flags = 0;
     const void *pattern_d_blob = nullptr, *pattern_d_offsets = nullptr, *pattern_d_ws = nullptr;
+    // the set of patterns loaded for bounded-mismatch scans (pgx_near_load): how many, the block and flags they were hashed
+    // with, the entries their table was sized for, and the device pointers of blob, offsets, max_mismatch and table + filter
+    // (workspace slots only near.hip uses; valid while near_loaded)
+    bool near_loaded = false;
+    uint32_t near_count = 0, near_block = 0, near_flags = 0;
+    uint64_t near_blocks = 0;
+    const void *near_d_blob = nullptr, *near_d_offsets = nullptr, *near_d_mismatch = nullptr, *near_d_ws = nullptr;
     // the concepts of the last formal concept decomposition (pgx_fcd*), kept for pgx_fcd_fetch: row / column indices of
     // all concepts end to end, the offsets of each concept in them (n + 1 entries), the ones left uncovered after each
     std::vector<int32_t> fcd_rows, fcd_cols;
