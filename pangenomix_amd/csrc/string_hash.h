@@ -1,6 +1,7 @@
-// Device helpers for byte strings kept in a blob with offsets, shared by dict.hip and prox.hip: a string's 16-byte chunks
-// read without touching a byte outside the blob, and the order-free 64-bit hash a group of DM_GROUP lanes computes of it
-// (dict.hip's header comment has the scheme).
+// Device helpers for byte strings kept in a blob with offsets: a string's span clamped into the blob and its 16-byte chunks
+// read without touching a byte outside it (dict.hip, prox.hip, pattern.hip, near.hip), the order-free 64-bit hash a group of
+// DM_GROUP lanes computes of a string (dict.hip and prox.hip; dict.hip's header comment has the scheme), and the 64-bit mix
+// under it, which annot.hip takes for its hashes of token lists.
 #pragma once
 #include "pgx_internal.h"
 

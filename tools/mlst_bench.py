@@ -10,7 +10,7 @@ one allele of every locus, half of them on the minus strand, and two schemes of 
 median / min / max of --runs runs after a warm-up, in one process on one machine:
   pattern_load, pattern_query   the two library calls with their transfers
   kernel_ms                     per-kernel time of ONE profiled load + query (pgx_profile_read; a run of its own)
-  yardstick                     scan_kernel (csrc/scan.hip, the code of the parent commit, unchanged here) on the same text with
+  yardstick                     scan_kernel (csrc/scan.hip) on the same text with
                                 window = seed and as many keys as the patterns have distinct seeds: the same per-position work
                                 without any verification; ratio = pattern_scan_kernel / scan_kernel
   call_alleles                  per genome over --genomes copies of the genome file (links to one file; each is read and parsed
@@ -21,8 +21,8 @@ and with three loci made novel by one substitution; per variant
   near_load, near_query         the two library calls with their transfers (all patterns loaded, m = 22, blocks of 19; the query
                                 with the patterns of the novel loci active, as call_alleles asks it), checked against host_near
   kernel_ms                     per-kernel time of ONE profiled load + query
-  yardstick                     pattern_scan_kernel (csrc/pattern.hip, the code of the parent commit, unchanged here) on the same
-                                text and scheme in the same process; ratio = near_scan_kernel / pattern_scan_kernel
+  yardstick                     pattern_scan_kernel (csrc/pattern.hip) on the same text and scheme in the same process; ratio =
+                                near_scan_kernel / pattern_scan_kernel
   call_alleles                  per genome with min_identity=95, with ctx (--genomes copies) and ctx=None (--near-host-genomes)
 and, on the genome without a novel locus, call_alleles with min_identity=None per genome, --runs runs with their spread, beside
 the figure the parent commit recorded in profiles/mlst_bench.json: the check that the default path did not get slower.
