@@ -1146,6 +1146,45 @@ int pgx_near_scan_dev(pgx_ctx *ctx, const uint8_t *d_text, uint64_t text_bytes, 
                       uint64_t n_blocks, uint32_t flags, const uint8_t *d_active, uint64_t *d_best, void *d_workspace,
                       size_t workspace_bytes, void *stream);
 
+/* Local alignment of pairs: Smith-Waterman with affine gaps on BLOSUM62, one best alignment per pair with its statistics
+ * and no traceback (the primitive under pangenomix_amd.ncbi.bidirectional_blast; the rules are DESIGN.md 6t). Sequence k of a
+ * set is the bytes [offsets[k], offsets[k + 1]) of its residues (offsets: n + 1 uint64, beginning with 0, not decreasing).
+ * A byte is a LETTER: A-Z and a-z are the same 26 letters, every other byte is one 27th letter; a letter's class is
+ * cluster_tables.h's (the 27th and J, O, U, X are class 20) and sub() is BLOSUM62 over the classes. Pair p aligns
+ * q = sequence pair_a[p] of set 1 (m residues) with s = sequence pair_b[p] of set 2 (n residues); a gap of k costs 11 + k:
+ *   E[i][j] = max(E[i][j-1] - 1, H[i][j-1] - 12)        F[i][j] = max(F[i-1][j] - 1, H[i-1][j] - 12)
+ *   H[i][j] = max(0, H[i-1][j-1] + sub(q[i], s[j]), E[i][j], F[i][j])       borders: H = 0, E = F = minus infinity
+ * On equal values the alternative written first wins (extension before opening; 0, diagonal, E, F). Every value carries the
+ * statistics of the path it was chosen from: a diagonal step from a cell with H = 0 starts a path at (i, j); a diagonal step
+ * adds a column and, for the same LETTER, an identity; an opening adds a column and a gap opening; an extension a column.
+ * The result is the cell of maximum H, ties to the smallest i, then the smallest j:
+ *   out[p] = { score, q_start, q_end, s_start, s_end, n_ident, n_cols, n_gapopen }    int32, positions 0-based inclusive
+ * score, q_end and s_end are always written; the other five only where score >= min_score[p] and score > 0, and are 0
+ * elsewhere (a score-only pass runs over every pair, the pass with statistics over those pairs alone). A pair with an empty
+ * sequence gives eight zeros. No atomics: the same input gives the same bytes on every call.
+ * A sequence of a pair longer than pgx_sw_max_length() (4,096), a pair index outside its set and decreasing offsets are
+ * PGX_ERR_INVALID: the host entry finds them before anything is launched or written; the device entry's kernels skip such
+ * a pair (eight zeros), never read outside what the offsets name, and the call then fails.
+ *   pgx_sw_pairs      HOST pointers. Orders the pairs by the kernel's steps (longest first) before it launches.
+ *   pgx_sw_pairs_dev  the caller's DEVICE pointers (offsets 8-byte, the other arrays 4-byte aligned) and stream; pairs run in
+ *                     the caller's order. max_len: no sequence of a pair is longer (1..pgx_sw_max_length(); a longer one
+ *                     is refused as above). Workspace: pgx_sw_workspace_bytes(ctx, n_pairs, max_len) bytes, 16-byte aligned
+ *                     (0 for sizes that are refused). Plain launches on `stream`, which is synchronised once at the end; no
+ *                     allocation; inputs are not written, nothing outside out and the workspace is.
+ * pgx_sw_strip_width(): the query positions one lane group holds at a time (the kernel's strip).
+ * pgx_sw_last_stats_pairs(): how many pairs of the context's last call took the pass with statistics. */
+uint32_t pgx_sw_max_length(void);
+uint32_t pgx_sw_strip_width(void);
+size_t pgx_sw_workspace_bytes(pgx_ctx *ctx, uint32_t n_pairs, uint32_t max_len);
+uint32_t pgx_sw_last_stats_pairs(pgx_ctx *ctx);
+int pgx_sw_pairs(pgx_ctx *ctx, const uint8_t *residues1, const uint64_t *offsets1, uint32_t n1, const uint8_t *residues2,
+                 const uint64_t *offsets2, uint32_t n2, const uint32_t *pair_a, const uint32_t *pair_b, uint32_t n_pairs,
+                 const int32_t *min_score, int32_t *out);
+int pgx_sw_pairs_dev(pgx_ctx *ctx, const uint8_t *d_residues1, const uint64_t *d_offsets1, uint32_t n1, const uint8_t *d_residues2,
+                     const uint64_t *d_offsets2, uint32_t n2, const uint32_t *d_pair_a, const uint32_t *d_pair_b, uint32_t n_pairs,
+                     const int32_t *d_min_score, uint32_t max_len, int32_t *d_out, void *d_workspace, size_t workspace_bytes,
+                     void *stream);
+
 /* feature names (pangenome.py:1944-1969) as fixed-width zero-padded ASCII records (numpy 'S<width>'):
  * <prefix><cluster>[<variant><member>]; variant NULL = gene names */
 int pgx_format_labels(const char *prefix, const char *variant, const int32_t *cluster, const int32_t *member,

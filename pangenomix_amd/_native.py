@@ -248,6 +248,13 @@ SIGNATURES = {
     'pgx_near_query': (C.c_int, [_P, _P, C.c_uint64, C.c_uint32, _P, _P]),
     'pgx_near_scan_dev': (C.c_int, [_P, _P, C.c_uint64, C.c_uint32, _P, _P, C.c_uint32, _P, C.c_uint32, C.c_uint64, C.c_uint32,
                                     _P, _P, _P, C.c_size_t, _P]),
+    'pgx_sw_max_length': (C.c_uint32, []),
+    'pgx_sw_strip_width': (C.c_uint32, []),
+    'pgx_sw_workspace_bytes': (C.c_size_t, [_P, C.c_uint32, C.c_uint32]),
+    'pgx_sw_last_stats_pairs': (C.c_uint32, [_P]),
+    'pgx_sw_pairs': (C.c_int, [_P, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P]),
+    'pgx_sw_pairs_dev': (C.c_int, [_P, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, C.c_uint32, _P, _P,
+                                   C.c_size_t, _P]),
     'pgx_genome_sets_diff':(C.c_int, [_P, _P, _P, C.c_uint64, _P, _P, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P]),
     'pgx_genome_sets_diff_dev': (C.c_int, [_P, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P]),
     'pgx_cluster_greedy': (C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(ClusterParams), _P, _P, _P, _P,
@@ -1111,6 +1118,36 @@ class Context(object):
         check(lib().pgx_near_scan_dev(self._h, d_text, int(text_bytes), int(separator), d_patterns, d_pattern_offsets,
                                       int(n_patterns), d_max_mismatch, int(block), int(n_blocks), int(flags), d_active, d_best,
                                       d_ws, int(ws_bytes), stream))
+
+    # -- local alignment of pairs (pangenomix_amd.ncbi.bidirectional_blast) -------------------------------------------------
+    def sw_pairs(self, residues1, offsets1, residues2, offsets2, pair_a, pair_b, min_score):
+        """out int32 [n_pairs, 8] = score, q_start, q_end, s_start, s_end, n_ident, n_cols, n_gapopen of the best local
+        alignment of sequence pair_a[p] of set 1 with sequence pair_b[p] of set 2 (pgx.h: pgx_sw_pairs); the five statistics
+        are 0 where score < min_score[p] (int32 [n_pairs], or one number for all) or score is 0."""
+        residues1, offsets1 = self._string_args(residues1, offsets1)
+        residues2, offsets2 = self._string_args(residues2, offsets2)
+        pair_a = np.ascontiguousarray(pair_a, dtype=np.uint32)
+        pair_b = np.ascontiguousarray(pair_b, dtype=np.uint32)
+        if pair_a.ndim != 1 or pair_a.shape != pair_b.shape:
+            raise ValueError('pair_a and pair_b must be 1-D arrays of equal length')
+        min_score = np.ascontiguousarray(np.broadcast_to(np.asarray(min_score, dtype=np.int32), pair_a.shape))
+        out = np.zeros((pair_a.size, 8), dtype=np.int32)
+        check(lib().pgx_sw_pairs(self._h, _ptr(residues1), _ptr(offsets1), offsets1.size - 1, _ptr(residues2), _ptr(offsets2),
+                                 offsets2.size - 1, _ptr(pair_a), _ptr(pair_b), pair_a.size, _ptr(min_score), _ptr(out)))
+        return out
+
+    def sw_workspace_bytes(self, n_pairs, max_len):
+        return int(lib().pgx_sw_workspace_bytes(self._h, int(n_pairs), int(max_len)))
+
+    def sw_last_stats_pairs(self):
+        """How many pairs of the last sw_pairs / sw_pairs_dev call took the pass with statistics."""
+        return int(lib().pgx_sw_last_stats_pairs(self._h))
+
+    def sw_pairs_dev(self, d_residues1, d_offsets1, n1, d_residues2, d_offsets2, n2, d_pair_a, d_pair_b, n_pairs, d_min_score,
+                     max_len, d_out, d_ws, ws_bytes, stream=0):
+        """The same on device memory (raw device addresses; synchronises `stream`, see pgx.h)."""
+        check(lib().pgx_sw_pairs_dev(self._h, d_residues1, d_offsets1, int(n1), d_residues2, d_offsets2, int(n2), d_pair_a,
+                                     d_pair_b, int(n_pairs), d_min_score, int(max_len), d_out, d_ws, int(ws_bytes), stream))
 
     def genome_sets_diff(self, a_rows, a_genomes, b_rows, b_genomes, n_rows, n_genomes):
         """(a_only, b_only) uint32 [n_genomes]: per genome the rows of the COO set A that B lacks and the other way round;

@@ -87,6 +87,8 @@ enum DevSlot : int {        // pgx_ctx::arena, through DevBuf
     // near.hip: the loaded set stays in the first four (blob, offsets, max_mismatch, table and filter); then a query's text,
     // its active flags and its best
     NR_SLOT_PATTERNS, NR_SLOT_OFFSETS, NR_SLOT_MISMATCH, NR_SLOT_WS, NR_SLOT_TEXT, NR_SLOT_ACTIVE, NR_SLOT_OUT,
+    // sw.hip: the two sets' residues, offsets, pairs, thresholds and order in one, the workspace, the results
+    SW_SLOT_RES1, SW_SLOT_RES2, SW_SLOT_IN, SW_SLOT_WS, SW_SLOT_OUT,
     DEV_SLOT_COUNT
 };
 enum HostSlot : int {       // pgx_ctx::host_scratch, through HostVec
@@ -152,6 +154,8 @@ struct pgx_ctx {
     uint32_t near_count = 0, near_block = 0, near_flags = 0;
     uint64_t near_blocks = 0;
     const void *near_d_blob = nullptr, *near_d_offsets = nullptr, *near_d_mismatch = nullptr, *near_d_ws = nullptr;
+    // of the last local alignment call (pgx_sw_pairs*): the pairs that took the pass with statistics
+    uint32_t sw_stats_pairs = 0;
     // the concepts of the last formal concept decomposition (pgx_fcd*), kept for pgx_fcd_fetch: row / column indices of
     // all concepts end to end, the offsets of each concept in them (n + 1 entries), the ones left uncovered after each
     std::vector<int32_t> fcd_rows, fcd_cols;

@@ -452,3 +452,40 @@ def mlst_genome(scheme, path, carried, n_bp=200000, n_contigs=5, seed=0, novel=(
             for j in range(0, len(contig), 80):
                 f.write(bytes(contig[j:j + 80]) + b'\n')
     return path
+
+
+def related_protein_set(seqs, seed=0, substituted=0.1, absent=0.15, indel=0.5, max_indel=8, max_flank=25, prefix='b'):
+    """A second protein set derived from `seqs` (bytes each), for pangenomix_amd.ncbi.bidirectional_blast: protein k is left
+    out with probability `absent`; a kept one has `substituted` of its sites replaced, with probability `indel` one planted
+    deletion or insertion of 1..max_indel residues away from its ends, and unrelated flanks of 0..max_flank random residues
+    on either side. Returns (names, sequences, origin): the names are <prefix><position>, origin[i] is the k it came from,
+    and the order is shuffled."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for k, raw in enumerate(seqs):
+        if rng.random() < absent:
+            continue
+        s = np.frombuffer(raw, dtype=np.uint8).copy()
+        if s.size:
+            ProteinSet._mutate(rng, s, substituted)
+        if s.size > 2 * max_indel + 4 and rng.random() < indel:
+            n = int(rng.integers(1, max_indel + 1))
+            at = int(rng.integers(max_indel, s.size - max_indel - n))
+            if rng.random() < 0.5:
+                s = np.concatenate([s[:at], s[at + n:]])
+            else:
+                s = np.concatenate([s[:at], AA20[rng.integers(0, 20, n)], s[at:]])
+        left, right = (AA20[rng.integers(0, 20, int(rng.integers(0, max_flank + 1)))] for _ in range(2))
+        out.append((k, np.concatenate([left, s, right]).tobytes()))
+    order = rng.permutation(len(out))
+    return (['%s%d' % (prefix, i) for i in range(len(out))], [out[j][1] for j in order],
+            np.array([out[j][0] for j in order], dtype=np.int64))
+
+
+def write_protein_fasta(path, names, seqs, wrap=60):
+    with open(path, 'w') as f:
+        for name, s in zip(names, seqs):
+            s = s.decode('ascii')
+            f.write('>%s synthetic protein\n' % name)
+            f.write('\n'.join(s[i:i + wrap] for i in range(0, len(s), wrap)) + '\n')
+    return path
