@@ -1172,9 +1172,13 @@ int pgx_near_scan_dev(pgx_ctx *ctx, const uint8_t *d_text, uint64_t text_bytes, 
  *                     (0 for sizes that are refused). Plain launches on `stream`, which is synchronised once at the end; no
  *                     allocation; inputs are not written, nothing outside out and the workspace is.
  * pgx_sw_strip_width(): the query positions one lane group holds at a time (the kernel's strip).
+ * pgx_sw_round_pairs(ctx, with_stats): the pairs that one round of the score pass (with_stats == 0) or of the pass with
+ * statistics can hold on the context's device, for the tests: a longer list makes every lane group take a further pair per
+ * round. 0 for a NULL ctx.
  * pgx_sw_last_stats_pairs(): how many pairs of the context's last call took the pass with statistics. */
 uint32_t pgx_sw_max_length(void);
 uint32_t pgx_sw_strip_width(void);
+uint32_t pgx_sw_round_pairs(pgx_ctx *ctx, int with_stats);
 size_t pgx_sw_workspace_bytes(pgx_ctx *ctx, uint32_t n_pairs, uint32_t max_len);
 uint32_t pgx_sw_last_stats_pairs(pgx_ctx *ctx);
 int pgx_sw_pairs(pgx_ctx *ctx, const uint8_t *residues1, const uint64_t *offsets1, uint32_t n1, const uint8_t *residues2,

@@ -250,6 +250,7 @@ SIGNATURES = {
                                     _P, _P, _P, C.c_size_t, _P]),
     'pgx_sw_max_length': (C.c_uint32, []),
     'pgx_sw_strip_width': (C.c_uint32, []),
+    'pgx_sw_round_pairs': (C.c_uint32, [_P, C.c_int]),
     'pgx_sw_workspace_bytes': (C.c_size_t, [_P, C.c_uint32, C.c_uint32]),
     'pgx_sw_last_stats_pairs': (C.c_uint32, [_P]),
     'pgx_sw_pairs': (C.c_int, [_P, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P]),
@@ -1138,6 +1139,11 @@ class Context(object):
 
     def sw_workspace_bytes(self, n_pairs, max_len):
         return int(lib().pgx_sw_workspace_bytes(self._h, int(n_pairs), int(max_len)))
+
+    def sw_round_pairs(self, with_stats):
+        """How many pairs one round of the score pass (with_stats false) or of the pass with statistics holds on this
+        device; a longer list gives every lane group a further pair per round (for the tests)."""
+        return int(lib().pgx_sw_round_pairs(self._h, 1 if with_stats else 0))
 
     def sw_last_stats_pairs(self):
         """How many pairs of the last sw_pairs / sw_pairs_dev call took the pass with statistics."""

@@ -304,9 +304,14 @@ __global__ __launch_bounds__(SW_COMPACT_THREADS) void sw_compact_kernel(const ui
     if (tid == SW_COMPACT_THREADS - 1) *n_out = counts[tid];
 }
 
-uint32_t sw_grid(pgx_ctx *ctx, uint32_t n_pairs, uint32_t per_cu) {
+// the most workgroups a pass launches: beyond them a lane group takes a further pair per round of the grid
+uint32_t sw_grid_cap(pgx_ctx *ctx, uint32_t per_cu) {
     const uint32_t cus = ctx->prop.multiProcessorCount > 0 ? (uint32_t)ctx->prop.multiProcessorCount : 1u;
-    return std::max(1u, std::min(ceil_div_u32(n_pairs, SW_GROUPS), cus * per_cu));
+    return cus * per_cu;
+}
+
+uint32_t sw_grid(pgx_ctx *ctx, uint32_t n_pairs, uint32_t per_cu) {
+    return std::max(1u, std::min(ceil_div_u32(n_pairs, SW_GROUPS), sw_grid_cap(ctx, per_cu)));
 }
 
 // head | the compacted list | the strips' last rows of either pass (the passes run one after the other)
@@ -449,6 +454,10 @@ size_t pgx_sw_workspace_bytes(pgx_ctx *ctx, uint32_t n_pairs, uint32_t max_len) 
 }
 
 uint32_t pgx_sw_last_stats_pairs(pgx_ctx *ctx) { return ctx ? ctx->sw_stats_pairs : 0; }
+
+uint32_t pgx_sw_round_pairs(pgx_ctx *ctx, int with_stats) {
+    return ctx ? sw_grid_cap(ctx, with_stats ? SW_WG_PER_CU_STATS : SW_WG_PER_CU_SCORE) * (uint32_t)SW_GROUPS : 0;
+}
 
 int pgx_sw_pairs(pgx_ctx *ctx, const uint8_t *residues1, const uint64_t *offsets1, uint32_t n1, const uint8_t *residues2,
                  const uint64_t *offsets2, uint32_t n2, const uint32_t *pair_a, const uint32_t *pair_b, uint32_t n_pairs,

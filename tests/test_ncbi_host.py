@@ -1,5 +1,5 @@
 """pangenomix_amd.ncbi on the host: known answers of the model host_sw, the model against a score-only
-Smith-Waterman and a full-matrix traceback written here with the same tie rules, candidate_pairs against brute force, the
+Smith-Waterman and a full-matrix traceback with the same tie rules (tests/sw_reference.py), candidate_pairs against brute force, the
 contract of bidirectional_blast, the recorded reports of tests/golden/blast and reciprocal_best_hits on them."""
 import math
 import os
@@ -8,21 +8,7 @@ import numpy as np
 import pytest
 
 from pangenomix_amd import ncbi, synth
-
-NEG = -10 ** 9
-CORE_LETTERS = np.frombuffer(b'ACDEFGHIKLMNQRSTVY', dtype=np.uint8)        # no W, no P: the flanks below match nothing
-
-
-def sub(a, b):
-    return int(ncbi.tables()[1][ncbi.letters_of(a)[0], ncbi.letters_of(b)[0]])
-
-
-def self_score(s):
-    return sum(sub(s[i:i + 1], s[i:i + 1]) for i in range(len(s)))
-
-
-def core(n, seed):
-    return CORE_LETTERS[np.random.default_rng(seed).integers(0, CORE_LETTERS.size, n)].tobytes()
+from sw_reference import core, pack, random_pairs, score_only, self_score, sub, traceback_sw, two_letter_relatives
 
 
 # ---- known answers ----------------------------------------------------------------------------------------------------------
@@ -64,76 +50,7 @@ def test_no_positive_cell():
     assert forward == [] and reverse == []
 
 
-# ---- the model against two others written here --------------------------------------------------------------------------------
-def pack(seqs):
-    off = np.zeros(len(seqs) + 1, dtype=np.uint64)
-    off[1:] = np.cumsum([len(s) for s in seqs])
-    return np.frombuffer(b''.join(seqs), dtype=np.uint8), off
-
-
-def score_only(q, s):
-    """best score and its first cell, row by row"""
-    best, H, F = (0, 0, 0), [0] * (len(s) + 1), [NEG] * (len(s) + 1)
-    for i in range(len(q)):
-        diag, left, E = 0, 0, NEG
-        for j in range(len(s)):
-            E = max(E - 1, left - 12)
-            F[j + 1] = max(F[j + 1] - 1, H[j + 1] - 12)
-            left, diag = max(0, diag + sub(q[i:i + 1], s[j:j + 1]), E, F[j + 1]), H[j + 1]
-            H[j + 1] = left
-            if left > best[0]:
-                best = (left, i, j)
-    return best
-
-
-def traceback_sw(q, s):
-    """The eight values by full matrices and a traceback: extension before opening, the diagonal before E, E before F."""
-    m, n = len(q), len(s)
-    H = np.zeros((m + 1, n + 1), dtype=np.int64)
-    E, F = np.full((m + 1, n + 1), NEG, dtype=np.int64), np.full((m + 1, n + 1), NEG, dtype=np.int64)
-    for i in range(1, m + 1):
-        for j in range(1, n + 1):
-            E[i, j] = max(E[i, j - 1] - 1, H[i, j - 1] - 12)
-            F[i, j] = max(F[i - 1, j] - 1, H[i - 1, j] - 12)
-            H[i, j] = max(0, H[i - 1, j - 1] + sub(q[i - 1:i], s[j - 1:j]), E[i, j], F[i, j])
-    best = int(H.max())
-    if best == 0:
-        return [0] * 8
-    i, j = [int(x) for x in np.argwhere(H == best)[0]]                    # row-major: the smallest i, then the smallest j
-    end = (i - 1, j - 1)
-    state, ident, cols, gaps = 'H', 0, 0, 0
-    while True:
-        if state == 'H':
-            d = H[i - 1, j - 1] + sub(q[i - 1:i], s[j - 1:j])
-            if d >= E[i, j] and d >= F[i, j]:
-                cols += 1
-                ident += ncbi.letters_of(q[i - 1:i])[0] == ncbi.letters_of(s[j - 1:j])[0]
-                if H[i - 1, j - 1] == 0:
-                    return [best, i - 1, end[0], j - 1, end[1], int(ident), cols, gaps]
-                i, j = i - 1, j - 1
-            else:
-                state = 'E' if E[i, j] >= F[i, j] else 'F'
-        elif state == 'E':
-            cols += 1
-            if not E[i, j - 1] - 1 >= H[i, j - 1] - 12:
-                gaps += 1
-                state = 'H'
-            j -= 1
-        else:
-            cols += 1
-            if not F[i - 1, j] - 1 >= H[i - 1, j] - 12:
-                gaps += 1
-                state = 'H'
-            i -= 1
-
-
-def random_pairs(count, letters, longest, seed):
-    rng = np.random.default_rng(seed)
-    letters = np.frombuffer(letters, dtype=np.uint8)
-    return [tuple(letters[rng.integers(0, letters.size, int(n))].tobytes() for n in rng.integers(1, longest + 1, 2))
-            for _ in range(count)]
-
-
+# ---- the model against two others (tests/sw_reference.py) -----------------------------------------------------------------------
 def test_scores_against_a_score_only_smith_waterman():
     for q, s in random_pairs(60, b'ACGT', 40, 11) + random_pairs(30, b'ACDEFGHIKLMNPQRSTVWYBZX', 60, 12):
         got = ncbi.host_sw(q, s, stats=False)
@@ -148,6 +65,18 @@ def test_statistics_against_a_traceback_where_ties_are_everywhere():
         assert ncbi.host_sw(q, s).tolist() == want, (q, s)
         gapped += want[7] > 0
     assert gapped > 30
+
+
+def test_statistics_against_a_traceback_past_one_strip():
+    """Two-letter relatives of 66..140 residues with one planted deletion of 1..5: longer than the kernel's strip, which
+    the pairs above are not, and every one gapped."""
+    pairs = two_letter_relatives()
+    assert len(pairs) >= 8
+    for q, s in pairs:
+        assert 66 <= len(q) <= 140 and 1 <= len(q) - len(s) <= 5 and set(q) <= set(b'AC')
+        want = traceback_sw(q, s)
+        assert ncbi.host_sw(q, s).tolist() == want, (q, s)
+        assert want[7] > 0, (q, s)
 
 
 @pytest.mark.parametrize('word_size', [3, 5])
